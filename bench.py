@@ -9,6 +9,9 @@ documents and sharded by doc-id range over the N ranks (strong scaling); per-sha
 one RCCL all-gather per batch.  `--gpus N` without a launcher starts the N ranks itself (a child
 `torch.distributed.run`, spawned before anything touches the GPU).  Rank 0 prints ONE JSON line.
 
+A plain run stages the index, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what
+the last timed step returned (num_hits, counts, ids, scores) as DIR/<name>.npy.  The line carries (p50_latency_ms_single_query
+is null unless --full runs the latency loop):
 roofline    : per kernel, from HIP events the library records around every launch on its stream inside the timed
               region (vq_profile_json).  `achieved` = bytes THIS data layout has to move per launch (bitmap words of
               dense lists, 4 B per id of scattered lists, 6 B per streamed posting, per-hit gathers as counted by the
@@ -16,6 +19,9 @@ roofline    : per kernel, from HIP events the library records around every launc
               posting-streaming accounting (6 B per posting of every list) is kept as `algorithmic_equiv`; it exceeds
               the peak where the layout reads dense lists as bitmaps, and says how fast a design that streams postings
               would have to read to keep up.
+--full adds the measurements and checks that run outside the timed steps (the --no-* options switch parts off):
+latency     : p50 of single-query batches through the same path.
+parity      : the last timed step's rows of the first probe triples against the CPU oracle (rank 0, N=1 only).
 cpu_baseline: the CPU oracle (C++ restatement of the reference algorithm, `kind: port`) timed on this host on a
               bounded sample of the same workload (rank 0, N=1 only).
 configs     : (N=1) the same accounting for BASELINE configs #2 (1 M docs, and the 100 M-doc index), #3 and #4,
@@ -315,6 +321,17 @@ def leg_summary(qps, ms, table):
     return {"qps": round(qps, 1), "ms_per_step": round(ms, 3), "kernel": name, "launch_ms": k.get("launch_ms"), "frac": k.get("frac"), "queries_per_launch": k.get("queries_per_launch")}
 
 
+def dump_outputs(dirname, outputs):
+    """The last timed step's (num_hits, counts, ids, scores), as the flat entry points hand them to a caller, to DIR/<name>.npy: the integer
+    arrays as float64 (exact: hit counts stay below 2^53, ids and counts are u32), scores as float32.  Row i answers request i of the batch;
+    ids / scores beyond counts[i] are the caller's zeros."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a, dt in zip(("num_hits", "counts", "ids", "scores"), outputs, (np.float64, np.float64, np.float64, np.float32)):
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a).astype(dt))
+    log(f"outputs of the last timed step written to {dirname}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -334,6 +351,10 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-query latency loop (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: single-query latency, oracle parity check of the last timed step, CPU baseline and the short runs "
+                         "of BASELINE configs #2-#4 (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (num_hits, counts, ids, scores) to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -387,11 +408,14 @@ def main():
     if rank == 0:
         log("index staged; running", args.steps, "steps of", args.batch, "queries")
     bench_chunks = int(os.environ["VQ_BENCH_CHUNKS"]) if os.environ.get("VQ_BENCH_CHUNKS") else None  # None: the searcher's default
-    qps, ms_step, p50, table, first_hits, reqs_json = bench.run(args.workload, args.batch, args.steps, args.warmup, latency=not args.no_latency, chunks=bench_chunks)
+    qps, ms_step, p50, table, first_hits, reqs_json = bench.run(args.workload, args.batch, args.steps, args.warmup, latency=args.full and not args.no_latency,
+                                                                chunks=bench_chunks)
 
     out = None
     if rank == 0:
         log(f"timed region done: {qps:.1f} q/s, {ms_step:.3f} ms per step")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, bench.last_outputs)
         spec = bench.spec
         out = {
             "metric": "queries/sec, 3-term AND on 100M-doc index (p50 latency and HBM fraction alongside)",
@@ -410,7 +434,7 @@ def main():
         legs = {"headline": leg_summary(qps, ms_step, table)}
         tables = {"headline": table}
         want_cpu = not args.no_cpu and args.cpu_seconds > 0
-        if world == 1 and not dist_on and args.workload in ("and", "or", "single") and (want_cpu or not args.no_parity):
+        if args.full and world == 1 and not dist_on and args.workload in ("and", "or", "single") and (want_cpu or not args.no_parity):
             n_tri = min(2, len(bench.meta.triples))
             t0 = time.time()
             ora = sample_oracle(bench.data, bench.meta, n_tri)
@@ -424,7 +448,7 @@ def main():
 
     # ---- the other named shapes, a few steps each (N=1), same accounting: the headline index with launches that hold every list several
     # times (what round 3 reported), BASELINE configs #2 - #4
-    if rank == 0 and world == 1 and not dist_on and not args.no_extra and args.workload == "and":
+    if args.full and rank == 0 and world == 1 and not dist_on and not args.no_extra and args.workload == "and":
 
         def short(name, b, workload, steps=8, note=None, launches=1, **kw):
             if not explicit_chunks:

@@ -32,6 +32,23 @@ def check(corpus, req, exact_scores=True):
     return got
 
 
+def test_synth_on_the_gpu_equals_the_torch_definition_on_the_cpu():
+    """synth.generate on a GPU (fused membership kernel, scores looked up on the device) writes the same arrays as its torch definition on
+    the CPU, for every store it makes, over a shard that starts inside the doc range"""
+    from veloci_amd import synth
+    spec = synth.SynthSpec(num_docs=2_000_003, num_terms=3000, triples=3, extra_probe_dfs=(700, 2_000_003), background_terms=20)
+    for lo, hi in ((0, None), (123_457, 1_900_000)):
+        (g, gm), (c, cm) = (synth.generate(spec, doc_lo=lo, doc_hi=hi, device=d) for d in ("cuda:0", "cpu"))
+        assert gm.triples == cm.triples and gm.extra_probes == cm.extra_probes and gm.background == cm.background
+        for name in ("token_to_anchor_score", "key_value_stores", "phrase_pair_to_anchor", "boost"):
+            gs, cs = getattr(g, name), getattr(c, name)
+            assert sorted(gs) == sorted(cs), name
+            for path in gs:
+                for a, b in zip(gs[path], cs[path]):
+                    assert (a is None and b is None) or np.array_equal(np.asarray(a), np.asarray(b)), (name, path)
+        assert sum(int(len(a)) for a in g.token_to_anchor_score["body.textindex.to_anchor_id_score"][1:2]) > 100_000
+
+
 def test_native_library_is_loaded():
     import veloci_amd
     assert veloci_amd.lib_path().endswith("libveloci_amd.so")

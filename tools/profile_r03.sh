@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 tag=$1; shift
 O=gpurun_out/r03_$tag; mkdir -p $O
-B="bench.py --steps 4 --warmup 2 --no-cpu --no-extra --no-latency $*"
+B="bench.py --full --steps 4 --warmup 2 --no-cpu --no-extra --no-latency $*"
 echo "== $tag: $B" > $O/log.txt
 [ -f gpurun_out/r03_counters.txt ] || rocprofv3 -L > gpurun_out/r03_counters.txt 2>&1
 run() {  # name, counters...

@@ -279,11 +279,19 @@ int vq_index_add_token_to_anchor_score(vq_index_builder* b, const char* path, ui
         p.offsets.assign(offsets, offsets + num_tokens + 1);
         const uint64_t n = offsets[num_tokens];
         if (n && (!anchors || !scores)) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_index_add_token_to_anchor_score: null arrays");
-        p.anchors.assign(anchors, anchors + n);
-        p.scores.assign(scores, scores + n);
-        for (uint32_t t = 0; t < num_tokens; ++t)
+        // copied and checked on host_threads() threads (billions of postings at the bench's scale)
+        p.anchors.resize(n);
+        p.scores.resize(n);
+        const size_t piece = size_t(1) << 24;
+        parallel_for((n + piece - 1) / piece, host_threads(), [&](size_t i) {
+            const size_t off = i * piece, m = std::min<size_t>(piece, n - off);
+            std::memcpy(p.anchors.data() + off, anchors + off, m * 4);
+            std::memcpy(p.scores.data() + off, scores + off, m * 4);
+        });
+        parallel_for(num_tokens, host_threads(), [&](size_t t) {
             for (uint64_t i = offsets[t] + 1; i < offsets[t + 1]; ++i)
                 if (!(anchors[i - 1] < anchors[i])) throw VelociError(VQ_ERR_INVALID_ARGUMENT, std::string("posting lists must be ascending and unique: ") + path);
+        });
         if (global_lens) p.global_lens.assign(global_lens, global_lens + num_tokens);
         b->b.postings[path] = std::move(p);
     });

@@ -49,10 +49,51 @@ extern const char* const TOKEN_VALUES;
 struct HostFst {
     std::vector<std::string> terms;  // bytewise sorted, ordinal == term id
 };
+// blocks of 64 MiB and more straight from mmap, as transparent huge pages where the kernel offers them: staging faults in and gives back tens
+// of gigabytes, 512 times fewer pages to map and unmap
+void* big_alloc(size_t bytes);
+void big_free(void* p, size_t bytes) noexcept;
+constexpr size_t kBigAlloc = size_t(64) << 20;
+
+// resize() leaves the elements uninitialised: staging overwrites every element of its big arrays (on several threads), a zero fill first would be
+// a single-threaded pass over tens of gigabytes
+template <class T>
+struct UninitAlloc : std::allocator<T> {
+    template <class U>
+    struct rebind {
+        using other = UninitAlloc<U>;
+    };
+    UninitAlloc() = default;
+    template <class U>
+    UninitAlloc(const UninitAlloc<U>&) noexcept {}
+    T* allocate(size_t n) {
+        return n * sizeof(T) >= kBigAlloc ? static_cast<T*>(big_alloc(n * sizeof(T))) : std::allocator<T>::allocate(n);
+    }
+    void deallocate(T* p, size_t n) noexcept {
+        if (n * sizeof(T) >= kBigAlloc) big_free(p, n * sizeof(T));
+        else std::allocator<T>::deallocate(p, n);
+    }
+    template <class U>
+    void construct(U* p) noexcept {
+        ::new (static_cast<void*>(p)) U;
+    }
+    template <class U, class... A>
+    void construct(U* p, A&&... a) {
+        ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
+    }
+};
+template <class T>
+using uninit_vector = std::vector<T, UninitAlloc<T>>;
+
+// host threads per index for request compilation and staging (the caller counts as one): VQ_HOST_THREADS, else the machine's, at most 16
+size_t host_threads();
+// fn(i) for i in [0, n) on `threads` threads (the caller included), items claimed one at a time; the first exception is rethrown
+void parallel_for(size_t n, size_t threads, const std::function<void(size_t)>& fn);
+
 struct HostPostings {
     std::vector<uint64_t> offsets;
-    std::vector<uint32_t> anchors;
-    std::vector<uint32_t> scores;
+    uninit_vector<uint32_t> anchors;
+    uninit_vector<uint32_t> scores;
     std::vector<uint64_t> global_lens;  // empty: lengths of the arrays handed over are the global ones
 };
 struct HostKV {

@@ -63,7 +63,7 @@ LaunchTimer::~LaunchTimer() {
 
 // host threads per index for request compilation (the caller counts as one): VQ_HOST_THREADS, else the machine's, at most 16 (a GPU's share of
 // the host on an 8-GPU node)
-static size_t host_threads() {
+size_t host_threads() {
     static const size_t n = [] {
         const char* e = std::getenv("VQ_HOST_THREADS");
         size_t hw = std::max(1u, std::thread::hardware_concurrency());

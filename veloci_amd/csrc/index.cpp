@@ -2,8 +2,13 @@
 // Replaces Persistence::load / load_indices (reference src/persistence.rs:206-291, 393-410) at the
 // decoded-array level; the on-disk formats are not read here.
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstring>
+#include <exception>
+#include <mutex>
+#include <thread>
+#include <sys/mman.h>
 
 #include "engine.hpp"
 #include "text.hpp"
@@ -99,6 +104,41 @@ static void shard_subrange(const uint32_t* b, const uint32_t* e, uint32_t lo, ui
     *oe = std::lower_bound(*ob, e, hi);
 }
 
+void* big_alloc(size_t bytes) {
+    void* p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (p == MAP_FAILED) throw std::bad_alloc();
+    (void)madvise(p, bytes, MADV_HUGEPAGE);  // (a hint: without transparent huge pages the block is ordinary pages)
+    return p;
+}
+void big_free(void* p, size_t bytes) noexcept { munmap(p, bytes); }
+
+void parallel_for(size_t n, size_t threads, const std::function<void(size_t)>& fn) {
+    threads = std::min(threads, n);
+    if (threads <= 1) {
+        for (size_t i = 0; i < n; ++i) fn(i);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    std::mutex err_mu;
+    std::exception_ptr err;
+    auto body = [&] {
+        for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < n;) {
+            try {
+                fn(i);
+            } catch (...) {
+                std::lock_guard<std::mutex> g(err_mu);
+                if (!err) err = std::current_exception();
+                next.store(n, std::memory_order_relaxed);
+            }
+        }
+    };
+    std::vector<std::thread> workers;
+    for (size_t k = 1; k < threads; ++k) workers.emplace_back(body);
+    body();
+    for (auto& w : workers) w.join();
+    if (err) std::rethrow_exception(err);
+}
+
 std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
@@ -161,34 +201,59 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         idx->dict.emplace(path, std::move(d));
     }
 
-    for (auto& [path, p] : b.postings) {
+    // Staging of the posting stores runs on host_threads() threads: every list's rows, bitmap, directories and tile-packed image are written to
+    // regions sized up front (the same bytes as a list-by-list pass), the big arrays go to HBM in 256 MiB pieces side by side
+    const size_t nthreads = host_threads();
+    auto upload = [&](DevBuf& dst, const void* src, size_t n) {
+        const size_t piece = size_t(256) << 20;
+        parallel_for((n + piece - 1) / piece, nthreads, [&](size_t i) {
+            VQ_HIP(hipSetDevice(device));
+            const size_t off = i * piece;
+            VQ_HIP(hipMemcpy(dst.as<uint8_t>() + off, static_cast<const uint8_t*>(src) + off, std::min(piece, n - off), hipMemcpyHostToDevice));
+        });
+    };
+    for (const auto& kv : b.postings) {
+        const std::string& path = kv.first;
+        const HostPostings& p = kv.second;
         PostingStore ps;
         ps.num_tokens = uint32_t(p.offsets.size() - 1);
         ps.start.resize(ps.num_tokens);
         ps.len.resize(ps.num_tokens);
         ps.global_len.resize(ps.num_tokens);
         ps.max_raw.assign(ps.num_tokens, 0);
-        std::vector<uint32_t> docs;
-        std::vector<uint16_t> scores;
-        docs.reserve(p.anchors.size() + 4 * size_t(std::min<uint32_t>(ps.num_tokens, 1u << 20)));
+        // rows padded to a multiple of 4 entries: ids with the 0xFFFFFFFF sentinel, scores with 0
+        std::vector<uint64_t> src_at(ps.num_tokens);  // where the shard's part of row t starts in the arrays handed over
+        uint64_t total = 0;
         for (uint32_t t = 0; t < ps.num_tokens; ++t) {
             const uint32_t* rb = p.anchors.data() + p.offsets[t];
             const uint32_t* re = p.anchors.data() + p.offsets[t + 1];
             const uint32_t *sb, *se;
             shard_subrange(rb, re, lo, hi, &sb, &se);
-            ps.start[t] = docs.size();
+            src_at[t] = uint64_t(sb - p.anchors.data());
+            ps.start[t] = total;
             ps.len[t] = uint32_t(se - sb);
             ps.global_len[t] = p.global_lens.empty() ? uint64_t(re - rb) : p.global_lens[t];
-            append_padded(docs, sb, se);
-            const uint32_t* sc = p.scores.data() + (sb - p.anchors.data());
-            for (uint32_t i = 0; i < ps.len[t]; ++i) {
-                const uint16_t h = f32_to_f16_rne(float(sc[i]));  // non-negative: bit order == value order
-                scores.push_back(h);
-                ps.max_raw[t] = std::max(ps.max_raw[t], h);
-            }
-            while (scores.size() < docs.size()) scores.push_back(0);
+            total += (uint64_t(ps.len[t]) + 3u) & ~uint64_t(3);
         }
-        ps.total_padded = docs.size();
+        uninit_vector<uint32_t> docs(total);
+        uninit_vector<uint16_t> scores(total);
+        parallel_for(ps.num_tokens, nthreads, [&](size_t t) {
+            const uint64_t s0 = ps.start[t], n = ps.len[t], padded = (n + 3u) & ~uint64_t(3);
+            std::memcpy(docs.data() + s0, p.anchors.data() + src_at[t], n * 4);
+            const uint32_t* sc = p.scores.data() + src_at[t];
+            uint16_t most = 0;
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint16_t h = f32_to_f16_rne(float(sc[i]));  // non-negative: bit order == value order
+                scores[s0 + i] = h;
+                most = std::max(most, h);
+            }
+            for (uint64_t i = n; i < padded; ++i) {
+                docs[s0 + i] = 0xFFFFFFFFu;
+                scores[s0 + i] = 0;
+            }
+            ps.max_raw[t] = most;
+        });
+        ps.total_padded = total;
         // ---- bitmap images of the dense lists (reading a tile of a dense list becomes a straight 16 B/lane copy)
         ps.bm_start.assign(ps.num_tokens, -1);
         ps.rd_start.assign(ps.num_tokens, -1);
@@ -199,12 +264,14 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
             for (uint32_t t = 0; t < ps.num_tokens; ++t)
                 if (range >= 65536 && uint64_t(ps.len[t]) * 64 >= range) dense.push_back(t);
             if (!dense.empty()) {
-                std::vector<uint32_t> bits(words * dense.size(), 0u);
-                std::vector<uint32_t> rdir((blocks + 1) * dense.size(), 0u);
-                for (size_t k = 0; k < dense.size(); ++k) {
+                uninit_vector<uint32_t> bits(words * dense.size());
+                uninit_vector<uint32_t> rdir((blocks + 1) * dense.size());
+                parallel_for(dense.size(), nthreads, [&](size_t k) {
                     const uint32_t t = dense[k];
                     uint32_t* bw = bits.data() + words * k;
                     uint32_t* rd = rdir.data() + (blocks + 1) * k;
+                    std::memset(bw, 0, words * 4);
+                    std::memset(rd, 0, (blocks + 1) * 4);
                     const uint32_t* d = docs.data() + ps.start[t];
                     for (uint32_t i = 0; i < ps.len[t]; ++i) {
                         const uint32_t rel = d[i] - idx->bitmap_base;
@@ -214,31 +281,37 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
                     for (uint64_t bl = 1; bl <= blocks; ++bl) rd[bl] += rd[bl - 1];
                     ps.bm_start[t] = int64_t(words * k);
                     ps.rd_start[t] = int64_t((blocks + 1) * k);
-                }
+                });
                 ps.bitmaps.alloc(bits.size() * 4 + 16);
-                ps.bitmaps.upload(bits.data(), bits.size() * 4);
+                upload(ps.bitmaps, bits.data(), bits.size() * 4);
                 ps.rank_dir.alloc(rdir.size() * 4 + 16);
-                ps.rank_dir.upload(rdir.data(), rdir.size() * 4);
+                upload(ps.rank_dir, rdir.data(), rdir.size() * 4);
                 idx->device_bytes += ps.bitmaps.bytes + ps.rank_dir.bytes;
             }
         }
         // ---- tile directories of the lists that hold at least 1/4096 of the shard's docs (dense ones included: one can be the cover of an AND)
         ps.td_start.assign(ps.num_tokens, -1);
+        std::vector<uint32_t> tiled;  // those lists, ascending
         {
             const uint64_t range = uint64_t(hi) - lo;
             const uint64_t tiles = (idx->bitmap_words >> (kTileDirShift - 5)) + 3;  // (k_scan_probe reads every second entry, up to one behind its last 32768-doc tile)
-            std::vector<uint32_t> tdir;
             for (uint32_t t = 0; t < ps.num_tokens; ++t) {
                 if (range < 65536 || uint64_t(ps.len[t]) * 4096 < range) continue;
-                ps.td_start[t] = int64_t(tdir.size());
+                ps.td_start[t] = int64_t(tiled.size() * (tiles + 1));
+                tiled.push_back(t);
+            }
+            std::vector<uint32_t> tdir(tiled.size() * (tiles + 1));
+            parallel_for(tiled.size(), nthreads, [&](size_t j) {
+                const uint32_t t = tiled[j];
                 const uint32_t* d = docs.data() + ps.start[t];
+                uint32_t* out = tdir.data() + j * (tiles + 1);
                 uint32_t i = 0;
                 for (uint64_t k = 0; k <= tiles; ++k) {
                     const uint64_t bound = uint64_t(idx->bitmap_base) + (k << kTileDirShift);
                     while (i < ps.len[t] && d[i] < bound) ++i;
-                    tdir.push_back(i);
+                    out[k] = i;
                 }
-            }
+            });
             if (!tdir.empty()) {
                 ps.tile_dir.alloc(tdir.size() * 4 + 16);
                 ps.tile_dir.upload(tdir.data(), tdir.size() * 4);
@@ -246,35 +319,43 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
             }
         }
         // ---- tile-packed images of the same lists (k_scan_probe: cover stream and 16-bit array operands); sized in a first pass, then
-        // built and uploaded list by list (the host never holds a second copy of the whole store)
+        // built at their offsets into one host image each, and uploaded
         ps.pk_start.assign(ps.num_tokens, -1);
         ps.ak_start.assign(ps.num_tokens, -1);
         ps.gd_start.assign(ps.num_tokens, -1);
         {
             const uint64_t ptiles = (idx->bitmap_words >> (kProbeTileShift - 5)) + 2;  // (entry `one behind the last tile` included)
             uint64_t cov_gran = 0, arr_gran = 0;
-            std::vector<uint32_t> gd;
-            for (uint32_t t = 0; t < ps.num_tokens; ++t) {
-                if (ps.td_start[t] < 0) continue;
+            std::vector<uint32_t> gd(tiled.size() * (ptiles + 1));
+            std::vector<uint64_t> gran_of(tiled.size());
+            std::vector<uint32_t> most_of(tiled.size());
+            parallel_for(tiled.size(), nthreads, [&](size_t j) {
+                const uint32_t t = tiled[j];
                 const uint32_t* d = docs.data() + ps.start[t];
+                uint32_t* g = gd.data() + j * (ptiles + 1);
                 uint64_t gran = 0;
                 uint32_t i = 0, most = 0;
-                ps.gd_start[t] = int64_t(gd.size());
                 for (uint64_t k = 0; k <= ptiles; ++k) {
-                    gd.push_back(uint32_t(gran));
+                    g[k] = uint32_t(gran);
                     const uint64_t thi = uint64_t(idx->bitmap_base) + ((k + 1) << kProbeTileShift);
                     const uint32_t i0 = i;
                     while (i < ps.len[t] && d[i] < thi) ++i;
-                    const uint32_t g = (i - i0 + 7u) / 8u;
-                    most = std::max(most, g);
-                    gran += g;
+                    const uint32_t n8 = (i - i0 + 7u) / 8u;
+                    most = std::max(most, n8);
+                    gran += n8;
                 }
-                if (gran >= (1ull << 28)) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "posting list too long for its tile-packed image");
+                gran_of[j] = gran;
+                most_of[j] = most;
+            });
+            for (size_t j = 0; j < tiled.size(); ++j) {
+                const uint32_t t = tiled[j];
+                ps.gd_start[t] = int64_t(j * (ptiles + 1));
+                if (gran_of[j] >= (1ull << 28)) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "posting list too long for its tile-packed image");
                 ps.pk_start[t] = int64_t(cov_gran);
-                cov_gran += gran;
-                if (most <= 256) {  // no tile holds more than 2048 entries: the list can be an array operand
+                cov_gran += gran_of[j];
+                if (most_of[j] <= 256) {  // no tile holds more than 2048 entries: the list can be an array operand
                     ps.ak_start[t] = int64_t(arr_gran);
-                    arr_gran += gran;
+                    arr_gran += gran_of[j];
                 }
             }
             if (cov_gran) {
@@ -283,37 +364,38 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
                 ps.gdir.alloc(gd.size() * 4 + 16);
                 ps.gdir.upload(gd.data(), gd.size() * 4);
                 idx->device_bytes += ps.cov32.bytes + ps.arr16.bytes + ps.gdir.bytes;
-                std::vector<uint32_t> cov;
-                std::vector<uint16_t> arr;
-                for (uint32_t t = 0; t < ps.num_tokens; ++t) {
-                    if (ps.pk_start[t] < 0) continue;
+                uninit_vector<uint32_t> cov(cov_gran * 8);  // a granule: 8 entries (32 B of cov32, 16 B of arr16)
+                uninit_vector<uint16_t> arr(arr_gran * 8);
+                parallel_for(tiled.size(), nthreads, [&](size_t j) {
+                    const uint32_t t = tiled[j];
+                    const bool as_array = ps.ak_start[t] >= 0;
                     const uint32_t* d = docs.data() + ps.start[t];
                     const uint16_t* sc = scores.data() + ps.start[t];
-                    cov.clear();
-                    arr.clear();
+                    uint32_t* c = cov.data() + uint64_t(ps.pk_start[t]) * 8;
+                    uint16_t* a = as_array ? arr.data() + uint64_t(ps.ak_start[t]) * 8 : nullptr;
+                    uint64_t w = 0;  // entries written
                     uint32_t i = 0;
                     for (uint64_t k = 0; k <= ptiles; ++k) {
                         const uint64_t tlo = uint64_t(idx->bitmap_base) + (k << kProbeTileShift), thi = tlo + (1u << kProbeTileShift);
-                        for (; i < ps.len[t] && d[i] < thi; ++i) {
+                        for (; i < ps.len[t] && d[i] < thi; ++i, ++w) {
                             const uint32_t rel = uint32_t(d[i] - tlo);
-                            cov.push_back(rel << 16 | sc[i]);
-                            arr.push_back(uint16_t(rel));
+                            c[w] = rel << 16 | sc[i];
+                            if (a) a[w] = uint16_t(rel);
                         }
-                        while (cov.size() % 8) {
-                            cov.push_back(0xFFFFFFFFu);
-                            arr.push_back(0xFFFFu);
+                        for (; w % 8; ++w) {
+                            c[w] = 0xFFFFFFFFu;
+                            if (a) a[w] = 0xFFFFu;
                         }
                     }
-                    if (cov.empty()) continue;
-                    VQ_HIP(hipMemcpy(ps.cov32.as<uint8_t>() + uint64_t(ps.pk_start[t]) * 32, cov.data(), cov.size() * 4, hipMemcpyHostToDevice));
-                    if (ps.ak_start[t] >= 0) VQ_HIP(hipMemcpy(ps.arr16.as<uint8_t>() + uint64_t(ps.ak_start[t]) * 16, arr.data(), arr.size() * 2, hipMemcpyHostToDevice));
-                }
+                });
+                upload(ps.cov32, cov.data(), cov.size() * 4);
+                upload(ps.arr16, arr.data(), arr.size() * 2);
             }
         }
         ps.docs.alloc(docs.size() * 4 + 16);
-        ps.docs.upload(docs.data(), docs.size() * 4);
+        upload(ps.docs, docs.data(), docs.size() * 4);
         ps.scores.alloc(scores.size() * 2 + 16);
-        ps.scores.upload(scores.data(), scores.size() * 2);
+        upload(ps.scores, scores.data(), scores.size() * 2);
         idx->device_bytes += ps.docs.bytes + ps.scores.bytes;
         idx->postings.emplace(path, std::move(ps));
     }

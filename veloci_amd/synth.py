@@ -8,10 +8,14 @@ sorted and de-duplicated (src/create.rs:505-517), one text per doc with text_id 
 
 Membership of doc d in a probe list is a pure function of (seed, term key, d) — a 64-bit mix compared
 against the list's density — so any doc range [doc_lo, doc_hi) can be generated on its own and the
-shards of a sharded index are exactly the slices of the unsharded one.  The heavy per-doc hashing
-runs in torch (on the GPU when there is one); it is bench/test input generation, not the query path.
+shards of a sharded index are exactly the slices of the unsharded one.  The per-doc hashing is defined in
+torch (_h32) and runs so on the CPU; on a GPU, list membership comes from the fused kernel of
+libveloci_synth.so (csrc/synth.hip, the same arithmetic) and torch computes the score streams of the
+members.  It is bench/test input generation, not the query path.
 """
+import ctypes
 import math
+import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -111,8 +115,33 @@ def make_vocabulary(num_terms, seed):
     return sorted(out)
 
 
-def _bernoulli_list(dev, lo, hi, chunk, key, thr32, shared=None):
-    """docs d in [lo, hi) with h32(key, d) < thr32, or (shared) h32(shared_key, d) < shared_thr32; plus score streams."""
+_SYNTH_LIB = None
+
+
+def _synth_lib():
+    """veloci_amd/libveloci_synth.so (built with the package): the fused membership kernel for GPU generation"""
+    global _SYNTH_LIB
+    if _SYNTH_LIB is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libveloci_synth.so")
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: build the package first (__graft_entry__.build() / make -C veloci_amd/csrc)")
+        L = ctypes.CDLL(path)
+        L.vq_synth_member.restype = ctypes.c_int
+        L.vq_synth_member.argtypes = [ctypes.c_uint64] * 6 + [ctypes.c_void_p, ctypes.c_void_p]
+        _SYNTH_LIB = L
+    return _SYNTH_LIB
+
+
+def _member_docs(dev, lo, hi, chunk, key, thr32, shared):
+    """docs d in [lo, hi) (int64, ascending) with h32(key, d) < thr32, or (shared) h32(shared_key, d) < shared_thr32"""
+    if dev.type == "cuda":  # one fused pass per doc (the same arithmetic as _h32) instead of ~30 elementwise passes
+        mask = torch.empty(hi - lo, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _synth_lib().vq_synth_member(lo, hi - lo, _mix_int(key), thr32, _mix_int(shared[0]) if shared else 0, shared[1] if shared else 0,
+                                              mask.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"vq_synth_member: hip error {rc}")
+        return torch.nonzero(mask).squeeze(1) + lo
     docs_out = []
     for c0 in range(lo, hi, chunk):
         c1 = min(hi, c0 + chunk)
@@ -121,10 +150,16 @@ def _bernoulli_list(dev, lo, hi, chunk, key, thr32, shared=None):
         if shared is not None:
             m |= _h32(shared[0], d) < shared[1]
         docs_out.append(d[m])
-    docs = torch.cat(docs_out) if docs_out else torch.zeros(0, dtype=torch.int64, device=dev)
+    return torch.cat(docs_out) if docs_out else torch.zeros(0, dtype=torch.int64, device=dev)
+
+
+def _bernoulli_list(dev, lo, hi, chunk, key, thr32, shared=None):
+    """docs d in [lo, hi) with h32(key, d) < thr32, or (shared) h32(shared_key, d) < shared_thr32; plus score streams (pos * 13 + ntok).
+    Both as int64 tensors on `dev`."""
+    docs = _member_docs(dev, lo, hi, chunk, key, thr32, shared)
     pos = _h32(key ^ 0xA5A5A5A5, docs) % 16
     ntok = _h32(key ^ 0x5A5A5A5A, docs) % 13
-    return docs.to(torch.int32).cpu().numpy().view(np.uint32), (pos * 13 + ntok).to(torch.int16).cpu().numpy().astype(np.int64)
+    return docs, pos * 13 + ntok
 
 
 def _zipf_cdf(n):
@@ -154,8 +189,9 @@ def generate(spec: SynthSpec, doc_lo=0, doc_hi=None, device=None):
     used = set(slots)
 
     def add_list(tid, docs, stream, df_nominal):
-        table = token_score_table(max(int(df_nominal), 1)).reshape(-1)
-        lists[tid] = (docs, table[stream].astype(np.uint32))
+        """docs / stream: int64 tensors (kept where they were made until the CSR below is filled)"""
+        table = torch.from_numpy(token_score_table(max(int(df_nominal), 1)).reshape(-1).astype(np.int64)).to(docs.device)
+        lists[tid] = (docs.to(torch.int32), table[stream].to(torch.int32))
 
     pairs = {}  # (t1, t2) -> anchors
     si = 0
@@ -170,7 +206,8 @@ def generate(spec: SynthSpec, doc_lo=0, doc_hi=None, device=None):
             p = (fr[x] - q) / (1.0 - q)
             docs, stream = _bernoulli_list(dev, lo, hi, spec.chunk, spec.seed ^ (tids[x] * 0x9E37 + 0x1234567), int(p * (1 << 32)), shared)
             add_list(tids[x], docs, stream, fr[x] * N)
-            tri_docs.append(docs)
+            if spec.with_phrase:
+                tri_docs.append(docs.to(torch.int32).cpu().numpy().view(np.uint32))
         meta.triples.append(tuple(terms[t].decode() for t in tids))
         if spec.with_phrase:
             for (x, y) in ((0, 1), (1, 2)):
@@ -199,7 +236,8 @@ def generate(spec: SynthSpec, doc_lo=0, doc_hi=None, device=None):
         df = max(int(0.1 * N / r), 1)
         docs = np.unique(rng.integers(0, N, int(df * 1.02) + 8, dtype=np.int64))[:df].astype(np.uint32)
         docs = docs[(docs >= lo) & (docs < hi)]
-        stream = (_h32(spec.seed ^ (tid * 0x9E37 + 0x2468ACE), torch.from_numpy(docs.astype(np.int64))) % (16 * 13)).numpy()
+        docs = torch.from_numpy(docs.astype(np.int64))
+        stream = _h32(spec.seed ^ (tid * 0x9E37 + 0x2468ACE), docs) % (16 * 13)
         add_list(tid, docs, stream, df)
         meta.background.append(terms[tid].decode())
 
@@ -210,14 +248,16 @@ def generate(spec: SynthSpec, doc_lo=0, doc_hi=None, device=None):
     offsets = np.zeros(T + 1, np.uint64)
     offsets[1:] = np.cumsum(lens)
     total = int(offsets[-1])
-    anchors = np.zeros(total, np.uint32)
-    scores = np.zeros(total, np.uint32)
+    anchors = np.empty(total, np.uint32)  # (every posting is written below: the lists cover [0, total) back to back)
+    scores = np.empty(total, np.uint32)
     for tid in sorted(lists):  # (every list is let go of as soon as it is copied: the generator never holds the postings twice)
         docs, sc = lists.pop(tid)
         o = int(offsets[tid])
-        anchors[o:o + len(docs)] = docs
-        scores[o:o + len(docs)] = sc
+        torch.from_numpy(anchors[o:o + len(docs)].view(np.int32)).copy_(docs)
+        torch.from_numpy(scores[o:o + len(docs)].view(np.int32)).copy_(sc)
         del docs, sc
+    if dev.type == "cuda":
+        torch.cuda.empty_cache()  # (the lists' device memory goes back before the index is staged)
     data.add_token_to_anchor_score("body.textindex.to_anchor_id_score", offsets, anchors, scores, None)
     meta.local_lens["body.textindex.to_anchor_id_score"] = lens
     if spec.with_t2t:

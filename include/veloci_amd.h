@@ -72,7 +72,8 @@ void vq_index_builder_free(vq_index_builder*);
 
 /* Term dictionary of "<field>.textindex" — replaces `indices.fst[path]`
  * (src/persistence.rs:59; built at src/create/create_fulltext.rs:53-80).
- * Terms are UTF-8, bytewise sorted, ordinal == term id. */
+ * Terms are UTF-8, bytewise sorted, ordinal == term id.  Any plane: the fuzzy / prefix scan (k_dict_scan) stages the code points as u16
+ * when all of them are below U+10000 and as u32 otherwise; query terms of any length up to 2^20 - 1 code points. */
 int vq_index_add_fst(vq_index_builder*, const char* path, uint32_t num_terms,
                      const uint8_t* term_bytes, const uint64_t* term_offsets /* [num_terms+1] */);
 

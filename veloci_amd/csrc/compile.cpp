@@ -2752,20 +2752,12 @@ static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable&
     fp.lev = clamped_lev(p);
     fp.check_prefix = p.starts_with || fp.lev != 0;  // :302
     const auto cps = vqtext::decode_utf8(p.terms[0]);
-    if (!dit->second.bmp_only) {
+    if (cps.size() >= kDictMaxPattern) {
         fp.status = ERR_UNSUPPORTED;
-        fp.error = "fuzzy / prefix search on " + fp.path + ": dictionary holds code points above U+FFFF";
-    } else if (cps.size() > 64) {
-        fp.status = ERR_UNSUPPORTED;
-        fp.error = "fuzzy / prefix search with a term longer than 64 characters";
+        fp.error = "fuzzy / prefix search with a term of " + std::to_string(cps.size()) + " characters (the dictionary scan takes fewer than " +
+                   std::to_string(kDictMaxPattern) + ")";
     }
-    for (uint32_t cp : cps) {
-        if (cp > 0xFFFFu && fp.status == 0) {
-            fp.status = ERR_UNSUPPORTED;
-            fp.error = "fuzzy / prefix search with a code point above U+FFFF";
-        }
-        fp.query.push_back(uint16_t(fp.ci ? vqtext::lower_cp(cp) : cp));
-    }
+    for (uint32_t cp : cps) fp.query.push_back(fp.ci ? vqtext::lower_cp(cp) : cp);
     table.emplace(key, std::move(fp));
 }
 static void probe_tree(const Index& idx, const SearchRequest& r, FuzzyTable& table) {

@@ -159,12 +159,12 @@ struct DevBuf {
 struct Dictionary {  // term dictionary of one text field
     std::vector<std::string> terms;
     std::unordered_map<std::string, std::vector<uint32_t>> lower_map;  // lowercase(term) -> ascending term ids (exact lookups)
-    // device image for the fuzzy / prefix scan (k_dict_scan): code points as u16, raw and lower-cased
-    bool bmp_only = true;  // false: some term has a code point above U+FFFF -> no device image, fuzzy unsupported on this field
-    bool low_exact = true; // false: the lower-cased image is not str::to_lowercase of every term (U+0130): matches are scored on the host
-    DevBuf d_off;          // u32 [T + 1]
-    DevBuf d_raw;          // u16
-    DevBuf d_low;          // u16
+    // device image for the fuzzy / prefix scan (k_dict_scan): one code point per element, raw and lower-cased per code point
+    uint32_t char_bytes = 2;  // 2: every code point is below U+10000 (u16 image); 4: some term has one above U+FFFF (u32 image)
+    bool low_exact = true;    // false: the lower-cased image is not str::to_lowercase of every term (U+0130): matches are scored on the host
+    DevBuf d_off;             // u32 [T + 1]
+    DevBuf d_raw;             // u16 or u32 (char_bytes)
+    DevBuf d_low;             // u16 or u32 (char_bytes)
 };
 
 struct Index;
@@ -172,7 +172,7 @@ struct PostingStore;
 struct FuzzyProbe {  // one dictionary scan of a batch (get_text_lines_from_fst, search_field.rs:68-99)
     std::string key;
     std::string path;                 // "<field>.textindex"
-    std::vector<uint16_t> query;      // code points of the ORIGINAL term (lower-cased when case-insensitive)
+    std::vector<uint32_t> query;      // code points of the ORIGINAL term (lower-cased when case-insensitive)
     uint32_t max_d = 0;
     bool transposition = false, prefix = false, ci = true;
     std::vector<uint32_t> matches;    // ascending term ids == FST stream order

@@ -216,23 +216,57 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
     for (auto& kv : table)
         if (kv.second.status == 0) todo.push_back(&kv.second);
     if (todo.empty()) return;
-    auto image_of = [&](const FuzzyProbe& fp) {  // the dictionary image a probe scans
+    auto image_of = [&](const FuzzyProbe& fp) -> const void* {  // the dictionary image a probe scans
         const Dictionary& d = idx.dict.at(fp.path);
-        return fp.ci ? d.d_low.as<uint16_t>() : d.d_raw.as<uint16_t>();
+        return fp.ci ? d.d_low.p : d.d_raw.p;
     };
-    // probes of one image next to each other: a launch scans ONE image for a run of probes (blocks answer 16 probes per pass over their terms)
-    std::stable_sort(todo.begin(), todo.end(), [&](const FuzzyProbe* a, const FuzzyProbe* b) { return image_of(*a) < image_of(*b); });
+    // k_dict_scan takes a 16-bit image and a query of <= 64 code points below U+10000 inline; every other probe goes to k_dict_scan_wide, with
+    // its code points as u32 in a side pool
+    auto pooled = [&](const FuzzyProbe& fp) {
+        bool wide = idx.dict.at(fp.path).char_bytes != 2 || fp.query.size() > 64;
+        for (uint32_t cp : fp.query) wide = wide || cp > 0xFFFFu;
+        return wide;
+    };
+    // probes of one image (and form) next to each other: a launch scans ONE image for a run of probes (blocks answer 16 probes per pass over their terms)
+    std::stable_sort(todo.begin(), todo.end(), [&](const FuzzyProbe* a, const FuzzyProbe* b) {
+        const void *ia = image_of(*a), *ib = image_of(*b);
+        return ia != ib ? ia < ib : pooled(*a) < pooled(*b);
+    });
     std::vector<DictProbe> probes(todo.size());
-    std::vector<uint8_t> host_scored(todo.size(), 0);
+    std::vector<DictProbeW> wprobes;  // indexed like `probes` (only the pooled ones are filled in); empty when no probe is pooled
+    std::vector<uint32_t> pool;
+    std::vector<uint8_t> host_scored(todo.size(), 0), is_pooled(todo.size(), 0);
     for (size_t i = 0; i < todo.size(); ++i) {
         const FuzzyProbe& fp = *todo[i];
+        const auto lcps = vqtext::decode_utf8(fp.lower_term);  // scoring side: the lower-cased term as a whole (search_field.rs:298-300)
+        if (pooled(fp)) {
+            if (wprobes.empty()) wprobes.resize(todo.size());
+            is_pooled[i] = 1;
+            DictProbeW& W = wprobes[i];
+            std::memset(&W, 0, sizeof W);
+            W.m = uint32_t(fp.query.size());
+            W.max_d = fp.max_d;
+            W.flags = (fp.transposition ? 1u : 0u) | (fp.prefix ? 2u : 0u);
+            W.q_off = uint32_t(pool.size());
+            pool.insert(pool.end(), fp.query.begin(), fp.query.end());
+            // the device scores a hit with a bit-vector over the lower-cased term in one 64-bit word: longer ones are scored on the host
+            if (lcps.size() <= 64 && idx.dict.at(fp.path).low_exact) {
+                W.lm = uint32_t(lcps.size());
+                W.lq_off = uint32_t(pool.size());
+                pool.insert(pool.end(), lcps.begin(), lcps.end());
+                if (fp.ci && lcps == fp.query) W.flags |= 4u;  // (then m <= 64: the whole query is staged in LDS)
+            } else {
+                W.lm = 0xFFFFFFFFu;
+                host_scored[i] = 1;
+            }
+            continue;
+        }
         DictProbe& P = probes[i];
         std::memset(&P, 0, sizeof P);
         P.m = uint32_t(fp.query.size());
         P.max_d = fp.max_d;
         P.flags = (fp.transposition ? 1u : 0u) | (fp.prefix ? 2u : 0u);
-        for (size_t j = 0; j < fp.query.size(); ++j) P.query[j] = fp.query[j];
-        const auto lcps = vqtext::decode_utf8(fp.lower_term);  // scoring side: the lower-cased term as a whole (search_field.rs:298-300)
+        for (size_t j = 0; j < fp.query.size(); ++j) P.query[j] = uint16_t(fp.query[j]);  // (all below U+10000: not pooled)
         bool bmp = lcps.size() <= 64 && idx.dict.at(fp.path).low_exact;
         for (uint32_t cp : lcps) bmp = bmp && cp <= 0xFFFFu;
         if (bmp) {
@@ -249,9 +283,15 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
         }
     }
     DevBuf &d_probes = ws.d_probe_desc, &d_count = ws.d_probe_counts, &d_out = ws.d_probe_ids;
-    d_probes.ensure(probes.size() * sizeof(DictProbe));
+    // one descriptor buffer: [DictProbe x N][DictProbeW x N][pool]
+    const size_t w_at = align_up(probes.size() * sizeof(DictProbe), 256), pool_at = w_at + align_up(wprobes.size() * sizeof(DictProbeW), 256);
+    d_probes.ensure(pool_at + pool.size() * 4 + 16);
     d_count.ensure(64);
     VQ_HIP(hipMemcpyAsync(d_probes.p, probes.data(), probes.size() * sizeof(DictProbe), hipMemcpyHostToDevice, st));
+    if (!wprobes.empty()) {
+        VQ_HIP(hipMemcpyAsync(d_probes.as<uint8_t>() + w_at, wprobes.data(), wprobes.size() * sizeof(DictProbeW), hipMemcpyHostToDevice, st));
+        if (!pool.empty()) VQ_HIP(hipMemcpyAsync(d_probes.as<uint8_t>() + pool_at, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, st));
+    }
     uint32_t cap = uint32_t(std::max<size_t>(64 * todo.size(), 1u << 16));  // matches of the whole batch share one output array
     std::vector<DictMatch> recs;
     for (int pass = 0; pass < 2; ++pass) {  // pass 1 only when the matches outgrew the first guess (the count is exact then)
@@ -266,10 +306,16 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
             LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_SCAN, 0, dict_bytes, todo.size());
             for (size_t g0 = 0; g0 < todo.size();) {  // one launch per run of probes over the same image
                 size_t g1 = g0 + 1;
-                while (g1 < todo.size() && image_of(*todo[g1]) == image_of(*todo[g0])) ++g1;
+                while (g1 < todo.size() && image_of(*todo[g1]) == image_of(*todo[g0]) && is_pooled[g1] == is_pooled[g0]) ++g1;
                 const Dictionary& d = idx.dict.at(todo[g0]->path);
-                launch_dict_scan(st, d_probes.as<DictProbe>() + g0, uint32_t(g0), uint32_t(g1 - g0), d.d_off.as<uint32_t>(), image_of(*todo[g0]), d.d_low.as<uint16_t>(),
-                                 uint32_t(d.terms.size()), d_count.as<uint32_t>(), cap, d_out.as<DictMatch>());
+                if (is_pooled[g0])
+                    launch_dict_scan_wide(st, d.char_bytes, reinterpret_cast<const DictProbeW*>(d_probes.as<uint8_t>() + w_at) + g0,
+                                          reinterpret_cast<const uint32_t*>(d_probes.as<uint8_t>() + pool_at), uint32_t(g0), uint32_t(g1 - g0), d.d_off.as<uint32_t>(),
+                                          image_of(*todo[g0]), d.d_low.p, uint32_t(d.terms.size()), d_count.as<uint32_t>(), cap, d_out.as<DictMatch>());
+                else
+                    launch_dict_scan(st, d_probes.as<DictProbe>() + g0, uint32_t(g0), uint32_t(g1 - g0), d.d_off.as<uint32_t>(),
+                                     static_cast<const uint16_t*>(image_of(*todo[g0])), d.d_low.as<uint16_t>(), uint32_t(d.terms.size()), d_count.as<uint32_t>(), cap,
+                                     d_out.as<DictMatch>());
                 layout += (d.d_off.bytes + d.d_low.bytes) * ((g1 - g0 + 15) / 16);  // ... this layout: once per 16 probes of one image
                 g0 = g1;
             }

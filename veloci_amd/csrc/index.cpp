@@ -176,27 +176,33 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         d.terms = f.terms;
         d.lower_map.reserve(d.terms.size());
         for (uint32_t i = 0; i < d.terms.size(); ++i) d.lower_map[vqtext::to_lower_utf8(d.terms[i])].push_back(i);
-        {  // device image for k_dict_scan: code points as u16 (raw + lower-cased), CSR over the terms
+        {  // device image for k_dict_scan: code points as u16 (raw + lower-cased), CSR over the terms; as u32 when some term has one above U+FFFF
             std::vector<uint32_t> off(d.terms.size() + 1, 0u);
-            std::vector<uint16_t> raw, low;
+            std::vector<uint32_t> raw, low;
             for (uint32_t i = 0; i < d.terms.size(); ++i) {
                 for (uint32_t cp : vqtext::decode_utf8(d.terms[i])) {
-                    if (cp > 0xFFFFu) d.bmp_only = false;
+                    if (cp > 0xFFFFu) d.char_bytes = 4;
                     if (cp == 0x130u) d.low_exact = false;  // lower-cases to TWO code points ("i" + U+0307): the image is per code point
-                    raw.push_back(uint16_t(cp));
-                    low.push_back(uint16_t(vqtext::lower_cp(cp)));
+                    raw.push_back(cp);
+                    low.push_back(vqtext::lower_cp(cp));
                 }
                 off[i + 1] = uint32_t(raw.size());
             }
-            if (d.bmp_only) {
-                d.d_off.alloc(off.size() * 4 + 16);
-                d.d_off.upload(off.data(), off.size() * 4);
-                d.d_raw.alloc(raw.size() * 2 + 16);
-                d.d_raw.upload(raw.data(), raw.size() * 2);
-                d.d_low.alloc(low.size() * 2 + 16);
-                d.d_low.upload(low.data(), low.size() * 2);
-                idx->device_bytes += d.d_off.bytes + d.d_raw.bytes + d.d_low.bytes;
-            }
+            auto image = [&](DevBuf& dst, const std::vector<uint32_t>& cps) {
+                if (d.char_bytes == 4) {
+                    dst.alloc(cps.size() * 4 + 16);
+                    dst.upload(cps.data(), cps.size() * 4);
+                } else {
+                    const std::vector<uint16_t> narrow(cps.begin(), cps.end());
+                    dst.alloc(narrow.size() * 2 + 16);
+                    dst.upload(narrow.data(), narrow.size() * 2);
+                }
+            };
+            d.d_off.alloc(off.size() * 4 + 16);
+            d.d_off.upload(off.data(), off.size() * 4);
+            image(d.d_raw, raw);
+            image(d.d_low, low);
+            idx->device_bytes += d.d_off.bytes + d.d_raw.bytes + d.d_low.bytes;
         }
         idx->dict.emplace(path, std::move(d));
     }

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "device_types.hpp"
 #include "kernels.hpp"
 #include "kernel_common.hpp"
@@ -2753,10 +2755,12 @@ void launch_scan_wide(hipStream_t st, uint32_t max_leaves, uint32_t max_scatter,
 
 // ====================================================================================================
 // k_dict_scan (K9) — fuzzy / prefix term expansion: one lane per dictionary term, Myers / Hyyrö bit-vector
-// edit distance of the query (pattern, <= 64 code points) against the term (text).  Decides exactly what the
-// reference's Levenshtein DFA accepts (search_field.rs:85-95): distance(term, query) <= max_d, with adjacent
-// transpositions at cost one when requested, or — for starts_with — the minimum over all prefixes of the term.
-// Code points are compared as stored (the host hands over the lower-cased image for case-insensitive scans).
+// edit distance of the query (pattern) against the term (text).  Decides exactly what the reference's Levenshtein DFA accepts
+// (search_field.rs:85-95): distance(term, query) <= max_d, with adjacent transpositions at cost one when requested, or — for starts_with —
+// the minimum over all prefixes of the term.  Code points are compared as stored (the host hands over the lower-cased image for
+// case-insensitive scans), widened to 32 bits: a code point above U+FFFF of the query never equals one of a 16-bit image.
+// Two forms of one body: k_dict_scan (16-bit image, queries of <= 64 BMP code points inline in the descriptor) and k_dict_scan_wide<CharT>
+// (16- or 32-bit image, queries of any length as 32-bit code points in a side pool; patterns longer than 64 take a banded recurrence).
 // ====================================================================================================
 namespace vq {
 
@@ -2765,9 +2769,9 @@ namespace vq {
 // by at most one per text character): most terms of a dictionary are out after two or three characters.
 // (`text` is either the LDS stage or the HBM image: the two callers are separate instantiations on purpose — a pointer selected at run time
 // between the two becomes a FLAT load, which costs several hundred cycles per character of every surviving pair)
-template <class Word>
-__device__ __forceinline__ bool dict_match(uint32_t m, uint32_t max_d, bool transposition, bool prefix, uint32_t n, const uint16_t* text,
-                                           const unsigned long long* peq_p, const uint16_t* q) {
+template <class Word, class CharT, class QT>
+__device__ __forceinline__ bool dict_match(uint32_t m, uint32_t max_d, bool transposition, bool prefix, uint32_t n, const CharT* text,
+                                           const unsigned long long* peq_p, const QT* q) {
     const Word one = 1;
     const Word top = one << (m - 1);
     Word Pv = m == sizeof(Word) * 8 ? ~Word(0) : ((one << m) - one), Mv = 0, prevEq = 0, prevD0 = ~Word(0);
@@ -2779,7 +2783,7 @@ __device__ __forceinline__ bool dict_match(uint32_t m, uint32_t max_d, bool tran
         if (c < 128u) Eq = (Word)peq_p[c];
         else {
             Eq = 0;
-            for (uint32_t j = 0; j < m; ++j) Eq |= (Word)(q[j] == c) << j;
+            for (uint32_t j = 0; j < m; ++j) Eq |= (Word)((uint32_t)q[j] == c) << j;
         }
         Word D0 = (((Eq & Pv) + Pv) ^ Pv) | Eq | Mv;
         if (transposition) D0 |= (((~prevD0) & Eq) << 1) & prevEq;  // Hyyrö 2003: adjacent transposition, cost one
@@ -2799,22 +2803,96 @@ __device__ __forceinline__ bool dict_match(uint32_t m, uint32_t max_d, bool tran
     return (prefix ? best : score) <= max_d;
 }
 
+// The same decision for a pattern of any length (the wide form sends patterns of more than 64 code points here).  Only the band
+// |row - column| <= kDictBand of the DP table can hold a value <= max_d (max_d <= 4, search_field.rs:87), and a table clamped to c = max_d + 1
+// follows the unclamped one exactly wherever that one is < c: cells outside the band count as c.  One column per text character, kept as
+// its 2 * kDictBand + 1 diagonals in registers (cell d = row i + d - kDictBand of column i); the pattern's code points under the band slide along
+// with one load per column.  Rows are 1-based: D[j][i] = distance of q[0, j) to text[0, i); transposition (restricted edit distance, what
+// the bit-vector form with Hyyrö's term computes): D[j - 2][i - 2] + 1 when q[j - 1] == text[i - 2] and q[j - 2] == text[i - 1].
+constexpr int kDictBand = 4;
+template <class CharT>
+__device__ __forceinline__ bool dict_match_band(const uint32_t* __restrict__ q, uint32_t m, uint32_t max_d, bool transposition, bool prefix, uint32_t n,
+                                                const CharT* text) {
+    constexpr int W = 2 * kDictBand + 1;
+    const uint32_t c = max_d + 1u;
+    const int mi = (int)m;
+    uint32_t prev[W], prev2[W], qw[W];
+    uint32_t eq_prev = 0u;  // bit d: row of diagonal d matched the previous column's character
+#pragma unroll
+    for (int d = 0; d < W; ++d) {
+        const int j = d - kDictBand;  // column 0: D[j][0] = j
+        prev[d] = (j < 0 || j > mi) ? c : ((uint32_t)j < c ? (uint32_t)j : c);
+        prev2[d] = c;
+        const int qi = d - kDictBand - 1;  // q index of diagonal d's row in column 0 (shifted by one before column 1)
+        qw[d] = (qi >= 0 && qi < mi) ? q[qi] : 0u;
+    }
+    uint32_t best = m < c ? m : c;  // the empty prefix
+    for (uint32_t i = 1; i <= n; ++i) {
+        const uint32_t t = text[i - 1u];
+        const int ii = (int)i;
+#pragma unroll
+        for (int d = 0; d < W - 1; ++d) qw[d] = qw[d + 1];
+        qw[W - 1] = ii + kDictBand - 1 < mi ? q[ii + kDictBand - 1] : 0u;
+        uint32_t cur[W];
+        uint32_t eq_cur = 0u, lo = c;
+#pragma unroll
+        for (int d = 0; d < W; ++d) {
+            const int j = ii + d - kDictBand;
+            uint32_t v;
+            if (j < 0 || j > mi) v = c;
+            else if (j == 0) v = i < c ? i : c;
+            else {
+                const bool eq = qw[d] == t;
+                eq_cur |= (eq ? 1u : 0u) << d;
+                v = prev[d] + (eq ? 0u : 1u);
+                const uint32_t up = (d > 0 ? cur[d > 0 ? d - 1 : 0] : c) + 1u, left = (d < W - 1 ? prev[d < W - 1 ? d + 1 : d] : c) + 1u;
+                v = up < v ? up : v;
+                v = left < v ? left : v;
+                // (on the band's edge diagonals the transposition term is >= kDictBand + 1 >= c anyway)
+                if (d > 0 && d < W - 1 && transposition && j >= 2 && i >= 2u && ((eq_cur >> (d - 1)) & 1u) && ((eq_prev >> (d + 1)) & 1u)) {
+                    const uint32_t tr = prev2[d] + 1u;
+                    v = tr < v ? tr : v;
+                }
+                v = v < c ? v : c;
+            }
+            cur[d] = v;
+            lo = v < lo ? v : lo;
+            if (prefix && j == mi) best = v < best ? v : best;
+        }
+#pragma unroll
+        for (int d = 0; d < W; ++d) {
+            prev2[d] = prev[d];
+            prev[d] = cur[d];
+        }
+        eq_prev = eq_cur;
+        if (lo >= c) return false;                                   // every cell of the band is clamped: none can come back under c
+        if (prefix && (best <= max_d || ii > mi + kDictBand)) break;  // a prefix is close enough / no later prefix is inside the band
+    }
+    if (prefix) return best <= max_d;
+    const int d = mi - (int)n + kDictBand;  // D[m][n]
+    if (d < 0 || d >= W) return false;
+    uint32_t v = c;
+#pragma unroll
+    for (int k = 0; k < W; ++k) v = k == d ? prev[k] : v;
+    return v <= max_d;
+}
+
 // Distance the reference SCORES a hit with (search_field.rs:691-732): full bit-vector recurrence of the lower-cased term (pattern, <= 64 code
 // points) over the lower-cased hit; TRANS: adjacent transpositions cost one (the scoring automaton), else plain Levenshtein (its fallback).
 // (peq_q: the pattern's match-mask table for code points < 128, or null)
-template <bool TRANS>
-__device__ __forceinline__ uint32_t dict_full_distance(const uint16_t* q, const unsigned long long* peq_q, uint32_t m, const uint16_t* __restrict__ text, uint32_t n) {
+template <bool TRANS, class CharT, class QT>
+__device__ __forceinline__ uint32_t dict_full_distance(const QT* q, const unsigned long long* peq_q, uint32_t m, const CharT* __restrict__ text, uint32_t n) {
     if (m == 0) return n;
     const unsigned long long top = 1ull << (m - 1);
     unsigned long long Pv = m == 64 ? ~0ull : ((1ull << m) - 1ull), Mv = 0ull, prevEq = 0ull, prevD0 = ~0ull;
     uint32_t score = m;
     for (uint32_t i = 0; i < n; ++i) {
-        const uint16_t c = text[i];
+        const CharT c = text[i];
         unsigned long long Eq;
         if (peq_q && c < 128u) Eq = peq_q[c];
         else {
             Eq = 0ull;
-            for (uint32_t j = 0; j < m; ++j) Eq |= (unsigned long long)(q[j] == c) << j;
+            for (uint32_t j = 0; j < m; ++j) Eq |= (unsigned long long)((uint32_t)q[j] == (uint32_t)c) << j;
         }
         unsigned long long D0 = (((Eq & Pv) + Pv) ^ Pv) | Eq | Mv;
         if (TRANS) D0 |= (((~prevD0) & Eq) << 1) & prevEq;
@@ -2832,9 +2910,9 @@ __device__ __forceinline__ uint32_t dict_full_distance(const uint16_t* q, const 
     return score;
 }
 
-constexpr uint32_t kDictGroup = 16;    // probes one block answers per pass over its terms
-constexpr uint32_t kDictStage = 4096;  // code points of a round's 256 terms staged in LDS (longer stretches are read from HBM)
-constexpr uint32_t kDictRounds = 8;    // rounds of 256 consecutive terms per block: the probes' match-mask tables are built once for all of them
+constexpr uint32_t kDictGroup = 16;          // probes one block answers per pass over its terms
+constexpr uint32_t kDictStageBytes = 8192;   // a round's 256 terms staged in LDS (4096 16-bit or 2048 32-bit code points; longer stretches are read from HBM)
+constexpr uint32_t kDictRounds = 8;          // rounds of 256 consecutive terms per block: the probes' match-mask tables are built once for all of them
 
 // One block = kDictRounds rounds of 256 consecutive dictionary terms (a round's code points are one contiguous stretch of the CSR image: staged into LDS with coalesced
 // loads) x a group of kDictGroup probes.  Per probe a match-mask table Peq[c] (bit j: query[j] == c) for c < 128 lives in LDS, so the per-character
@@ -2843,8 +2921,8 @@ constexpr uint32_t kDictRounds = 8;    // rounds of 256 consecutive terms per bl
 // The recurrence for a term of <= kDictShort ASCII code points staged in LDS: all its characters, then all their match masks, are read in two
 // batches of independent LDS loads — the character-by-character loop of dict_match pays two dependent LDS round trips per character.
 constexpr uint32_t kDictShort = 12;
-template <class Word>
-__device__ __forceinline__ bool dict_match_short(uint32_t m, uint32_t max_d, bool transposition, bool prefix, uint32_t n, const uint16_t* text,
+template <class Word, class CharT>
+__device__ __forceinline__ bool dict_match_short(uint32_t m, uint32_t max_d, bool transposition, bool prefix, uint32_t n, const CharT* text,
                                                  const unsigned long long* peq_p, bool* ascii) {
     uint32_t c[kDictShort];
     bool all_ascii = true;
@@ -2886,12 +2964,21 @@ __device__ __forceinline__ bool dict_match_short(uint32_t m, uint32_t max_d, boo
     return !dead && (prefix ? best : score) <= max_d;
 }
 
-__global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__ probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* __restrict__ off,
-                                                   const uint16_t* __restrict__ chars, const uint16_t* __restrict__ low_chars, uint32_t num_terms,
-                                                   uint32_t* __restrict__ out_count, uint32_t out_cap, DictMatch* __restrict__ out) {
+// POOL == false: k_dict_scan — 16-bit image, DictProbe with the query inline (<= 64 code points, all below U+10000).
+// POOL == true:  k_dict_scan_wide — DictProbeW, the query's code points (u32, any number) and the scoring side in `pool`; the first 64 code
+//                points are staged like the inline ones; patterns of more than 64 take dict_match_band, from the pool.
+// The group's parameters are packed into one scalar per probe: m | max_d << 8 | flags << 16 | valid << 31 (inline), m | max_d << 20 | flags
+// << 24 | valid << 31 (pool: m < 2^20, kDictMaxPattern).
+template <class CharT, bool POOL, class ProbeT>
+__device__ __forceinline__ void dict_scan_body(const ProbeT* __restrict__ probes, const uint32_t* __restrict__ pool, uint32_t probe_base, uint32_t n_probes,
+                                               const uint32_t* __restrict__ off, const CharT* __restrict__ chars, const CharT* __restrict__ low_chars,
+                                               uint32_t num_terms, uint32_t* __restrict__ out_count, uint32_t out_cap, DictMatch* __restrict__ out) {
+    using QT = typename std::conditional<POOL, uint32_t, uint16_t>::type;
+    constexpr uint32_t kStage = kDictStageBytes / sizeof(CharT);
+    constexpr uint32_t kMShift = POOL ? 20u : 8u, kFShift = POOL ? 24u : 16u, kMMask = (1u << kMShift) - 1u;
     __shared__ unsigned long long peq[kDictGroup][128];
-    __shared__ uint16_t stage[kDictStage];
-    __shared__ uint16_t qch[kDictGroup][64];
+    __shared__ CharT stage[kStage];
+    __shared__ QT qch[kDictGroup][64];
     __shared__ uint32_t pm[kDictGroup], pmaxd[kDictGroup], pflags[kDictGroup];
     __shared__ unsigned long long psig[kDictGroup];
     __shared__ uint32_t soff[257];                   // a round's term offsets, relative to its first code point
@@ -2902,7 +2989,14 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
     const uint32_t tid = threadIdx.x;
     const uint32_t p0 = blockIdx.y * kDictGroup;
     const uint32_t np = n_probes - p0 < kDictGroup ? n_probes - p0 : kDictGroup;
-    for (uint32_t x = tid; x < np * 64u; x += 256u) qch[x >> 6][x & 63u] = probes[p0 + (x >> 6)].query[x & 63u];
+    if constexpr (POOL) {
+        for (uint32_t x = tid; x < np * 64u; x += 256u) {
+            const ProbeT& P = probes[p0 + (x >> 6)];
+            qch[x >> 6][x & 63u] = (x & 63u) < P.m ? pool[P.q_off + (x & 63u)] : 0u;
+        }
+    } else {
+        for (uint32_t x = tid; x < np * 64u; x += 256u) qch[x >> 6][x & 63u] = probes[p0 + (x >> 6)].query[x & 63u];
+    }
     if (tid < kDictGroup) {
         pm[tid] = tid < np ? probes[p0 + tid].m : 0u;
         pmaxd[tid] = tid < np ? probes[p0 + tid].max_d : 0u;
@@ -2911,7 +3005,7 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
     for (uint32_t x = tid; x < kDictGroup * 128u; x += 256u) peq[x >> 7][x & 127u] = 0ull;
     __syncthreads();
     // the probes' tables, built once per block and used for all its kDictRounds x 256 terms: Peq[c] bit j = (query[j] == c), one LDS atomic
-    // per character of a query
+    // per character of a query (a pattern of more than 64 code points uses none of them)
     for (uint32_t x = tid; x < np * 64u; x += 256u) {
         const uint32_t p = x >> 6, j = x & 63u;
         if (j < pm[p] && qch[p][j] < 128u) atomicOr(&peq[p][qch[p][j]], 1ull << j);
@@ -2922,34 +3016,41 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
     // lower bound, no match is lost); a random dictionary term fails this test on a few register operations, without touching LDS.
     if (tid < kDictGroup) {
         unsigned long long sq = 0ull;
-        for (uint32_t j = 0; j < pm[tid]; ++j) sq |= 1ull << (((uint32_t)qch[tid][j] * 2654435761u) >> 26);
+        if constexpr (POOL) {
+            if (tid < np) {
+                const uint32_t* q = pool + probes[p0 + tid].q_off;
+                for (uint32_t j = 0; j < pm[tid]; ++j) sq |= 1ull << ((q[j] * 2654435761u) >> 26);
+            }
+        } else {
+            for (uint32_t j = 0; j < pm[tid]; ++j) sq |= 1ull << (((uint32_t)qch[tid][j] * 2654435761u) >> 26);
+        }
         psig[tid] = sq;
     }
     __syncthreads();
     // the group's parameters in scalar registers: the filter loop below touches no memory at all
-    uint32_t pk[kDictGroup], sg_lo[kDictGroup], sg_hi[kDictGroup];  // pk: m | max_d << 8 | flags << 16 | valid << 31
+    uint32_t pk[kDictGroup], sg_lo[kDictGroup], sg_hi[kDictGroup];
 #pragma unroll
     for (uint32_t p = 0; p < kDictGroup; ++p) {
-        pk[p] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pm[p] | (pmaxd[p] << 8) | (pflags[p] << 16) | (p < np ? 0x80000000u : 0u)));
+        pk[p] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pm[p] | (pmaxd[p] << kMShift) | (pflags[p] << kFShift) | (p < np ? 0x80000000u : 0u)));
         sg_lo[p] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)psig[p]);
         sg_hi[p] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(psig[p] >> 32));
     }
-    // A round's inputs — 257 offsets and up to kDictStage code points — are loaded into registers one round AHEAD: the block's rounds are
+    // A round's inputs — 257 offsets and up to kStage code points — are loaded into registers one round AHEAD: the block's rounds are
     // consecutive stretches of the image, so the next stretch starts where this one ends, and its loads are in flight while this round's
     // pairs are filtered and matched.
     const uint32_t total_chars = off[num_terms];
     const uint32_t first_t0 = blockIdx.x * kDictRounds * 256u;
     uint32_t n_off0 = 0, n_off1 = 0;
-    uint16_t n_ch[kDictStage / 256];
+    CharT n_ch[kStage / 256];
     auto prefetch = [&](uint32_t t0, uint32_t base) {
         if (t0 >= num_terms) return;  // uniform
         const uint32_t last = num_terms;  // off[] has num_terms + 1 entries
         n_off0 = off[t0 + tid <= last ? t0 + tid : last];
         if (tid == 0) n_off1 = off[t0 + 256u <= last ? t0 + 256u : last];
 #pragma unroll
-        for (uint32_t k = 0; k < kDictStage / 256u; ++k) {
+        for (uint32_t k = 0; k < kStage / 256u; ++k) {
             const uint32_t at = base + k * 256u + tid;
-            n_ch[k] = at < total_chars ? chars[at] : (uint16_t)0;
+            n_ch[k] = at < total_chars ? chars[at] : (CharT)0;
         }
     };
     uint32_t next_base = first_t0 < num_terms ? off[first_t0] : 0u;
@@ -2967,10 +3068,10 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
             qn = 0u;
         }
 #pragma unroll
-        for (uint32_t k = 0; k < kDictStage / 256u; ++k) stage[k * 256u + tid] = n_ch[k];
+        for (uint32_t k = 0; k < kStage / 256u; ++k) stage[k * 256u + tid] = n_ch[k];
         __syncthreads();
         const uint32_t stretch = soff[t_end - t0];
-        const uint32_t staged = stretch < kDictStage ? stretch : kDictStage;
+        const uint32_t staged = stretch < kStage ? stretch : kStage;
         next_base = base + stretch;
         prefetch(t0 + 256u, next_base);
         VQ_STAMP_AT(1)
@@ -2989,9 +3090,10 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
             const uint32_t nt_lo = ~(uint32_t)sig_t, nt_hi = ~(uint32_t)(sig_t >> 32);
 #pragma unroll
             for (uint32_t p = 0; p < kDictGroup; ++p) {
-                const uint32_t m = pk[p] & 0xFFu, max_d = (pk[p] >> 8) & 0xFFu;
-                const bool prefix = (pk[p] >> 17) & 1u, valid = pk[p] >> 31;
-                const bool len_ok = prefix || !(n > m + max_d || n + max_d < m);
+                const uint32_t m = pk[p] & kMMask, max_d = (pk[p] >> kMShift) & (POOL ? 0xFu : 0xFFu);
+                const bool prefix = (pk[p] >> (kFShift + 1u)) & 1u, valid = pk[p] >> 31;
+                // (a prefix of the term within max_d of the query has at least m - max_d code points: the pool form checks that too)
+                const bool len_ok = prefix ? (!POOL || n + max_d >= m) : !(n > m + max_d || n + max_d < m);
                 const uint32_t lacking = (uint32_t)__popc(sg_lo[p] & nt_lo) + (uint32_t)__popc(sg_hi[p] & nt_hi);
                 pmask |= (valid && len_ok && lacking <= max_d) ? (1u << p) : 0u;
             }
@@ -3029,6 +3131,13 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
             if (m == 0) {
                 match = prefix || n <= max_d;
                 done = true;
+            } else if (POOL && m > 64u) {
+                if constexpr (POOL) {
+                    const uint32_t* q = pool + probes[p0 + p].q_off;
+                    if (in_stage) match = dict_match_band(q, m, max_d, transposition, prefix, n, &stage[b]);
+                    else match = dict_match_band(q, m, max_d, transposition, prefix, n, chars + base + b);
+                }
+                done = true;
             } else if (in_stage && n <= kDictShort) {
                 if (m <= 32u) match = dict_match_short<uint32_t>(m, max_d, transposition, prefix, n, &stage[b], peq[p], &done);
                 else match = dict_match_short<unsigned long long>(m, max_d, transposition, prefix, n, &stage[b], peq[p], &done);
@@ -3045,19 +3154,22 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
             if (match) {  // rare: what the hit's score needs is computed here, on the lower-cased image
                 uint32_t info = 0;
                 if ((pflags[p] & 4u) && in_stage) {  // scored with the string and over the image it was matched with: everything is in LDS already
-                    const uint16_t* text = &stage[b];
+                    const CharT* text = &stage[b];
                     const uint32_t osa = dict_full_distance<true>(qch[p], peq[p], m, text, n), lev = dict_full_distance<false>(qch[p], peq[p], m, text, n);
                     bool starts = n >= m;
-                    for (uint32_t i = 0; starts && i < m; ++i) starts = text[i] == qch[p][i];
+                    for (uint32_t i = 0; starts && i < m; ++i) starts = (uint32_t)text[i] == (uint32_t)qch[p][i];
                     info = (osa < 255u ? osa : 255u) | ((lev < 255u ? lev : 255u) << 8) | ((starts ? 1u : 0u) << 16);
                 } else {
-                    const DictProbe& P = probes[p0 + p];
+                    const ProbeT& P = probes[p0 + p];
                     const uint32_t lm = P.lm;
                     if (lm != 0xFFFFFFFFu) {
-                        const uint16_t* text = low_chars + base + b;
-                        const uint32_t osa = dict_full_distance<true>(P.lquery, nullptr, lm, text, n), lev = dict_full_distance<false>(P.lquery, nullptr, lm, text, n);
+                        const CharT* text = low_chars + base + b;
+                        const QT* lq;
+                        if constexpr (POOL) lq = pool + P.lq_off;
+                        else lq = P.lquery;
+                        const uint32_t osa = dict_full_distance<true>(lq, nullptr, lm, text, n), lev = dict_full_distance<false>(lq, nullptr, lm, text, n);
                         bool starts = n >= lm;
-                        for (uint32_t i = 0; starts && i < lm; ++i) starts = text[i] == P.lquery[i];
+                        for (uint32_t i = 0; starts && i < lm; ++i) starts = (uint32_t)text[i] == (uint32_t)lq[i];
                         info = (osa < 255u ? osa : 255u) | ((lev < 255u ? lev : 255u) << 8) | ((starts ? 1u : 0u) << 16);
                     }
                 }
@@ -3070,11 +3182,39 @@ __global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__
     VQ_STAMP_FLUSH
 }
 
+__global__ __launch_bounds__(256) void k_dict_scan(const DictProbe* __restrict__ probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* __restrict__ off,
+                                                   const uint16_t* __restrict__ chars, const uint16_t* __restrict__ low_chars, uint32_t num_terms,
+                                                   uint32_t* __restrict__ out_count, uint32_t out_cap, DictMatch* __restrict__ out) {
+    dict_scan_body<uint16_t, false>(probes, nullptr, probe_base, n_probes, off, chars, low_chars, num_terms, out_count, out_cap, out);
+}
+
+template <class CharT>
+__global__ __launch_bounds__(256) void k_dict_scan_wide(const DictProbeW* __restrict__ probes, const uint32_t* __restrict__ pool, uint32_t probe_base, uint32_t n_probes,
+                                                        const uint32_t* __restrict__ off, const CharT* __restrict__ chars, const CharT* __restrict__ low_chars,
+                                                        uint32_t num_terms, uint32_t* __restrict__ out_count, uint32_t out_cap, DictMatch* __restrict__ out) {
+    dict_scan_body<CharT, true>(probes, pool, probe_base, n_probes, off, chars, low_chars, num_terms, out_count, out_cap, out);
+}
+
+static dim3 dict_scan_grid(uint32_t n_probes, uint32_t num_terms) {
+    return dim3((num_terms + 256u * kDictRounds - 1u) / (256u * kDictRounds), (n_probes + kDictGroup - 1u) / kDictGroup);
+}
+
 void launch_dict_scan(hipStream_t st, const DictProbe* d_probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const uint16_t* chars, const uint16_t* low_chars,
                       uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out) {
     if (!n_probes || !num_terms) return;
-    hipLaunchKernelGGL(k_dict_scan, dim3((num_terms + 256u * kDictRounds - 1u) / (256u * kDictRounds), (n_probes + kDictGroup - 1u) / kDictGroup), dim3(256), 0, st, d_probes, probe_base, n_probes, off, chars,
-                       low_chars, num_terms, out_count, out_cap, out);
+    hipLaunchKernelGGL(k_dict_scan, dict_scan_grid(n_probes, num_terms), dim3(256), 0, st, d_probes, probe_base, n_probes, off, chars, low_chars, num_terms, out_count,
+                       out_cap, out);
+}
+
+void launch_dict_scan_wide(hipStream_t st, uint32_t char_bytes, const DictProbeW* d_probes, const uint32_t* pool, uint32_t probe_base, uint32_t n_probes, const uint32_t* off,
+                           const void* chars, const void* low_chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out) {
+    if (!n_probes || !num_terms) return;
+    if (char_bytes == 4)
+        hipLaunchKernelGGL(k_dict_scan_wide<uint32_t>, dict_scan_grid(n_probes, num_terms), dim3(256), 0, st, d_probes, pool, probe_base, n_probes, off,
+                           static_cast<const uint32_t*>(chars), static_cast<const uint32_t*>(low_chars), num_terms, out_count, out_cap, out);
+    else
+        hipLaunchKernelGGL(k_dict_scan_wide<uint16_t>, dict_scan_grid(n_probes, num_terms), dim3(256), 0, st, d_probes, pool, probe_base, n_probes, off,
+                           static_cast<const uint16_t*>(chars), static_cast<const uint16_t*>(low_chars), num_terms, out_count, out_cap, out);
 }
 
 }  // namespace vq

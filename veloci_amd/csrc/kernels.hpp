@@ -13,6 +13,13 @@ struct DictProbe {  // one fuzzy / prefix scan of a dictionary (k_dict_scan)
     uint16_t query[64];            // match side: the ORIGINAL term (lower-cased per code point when case-insensitive)
     uint16_t lquery[64];           // scoring side: the lower-cased term (search_field.rs:298-300); lm == 0xFFFFFFFF: the host scores the matches
 };
+struct DictProbeW {  // one scan of k_dict_scan_wide: the query's code points as u32 in a side pool (any length, any plane)
+    uint32_t m, max_d, flags, lm;  // as DictProbe (m < kDictMaxPattern)
+    uint32_t q_off;                // pool[q_off, + m): match side
+    uint32_t lq_off;               // pool[lq_off, + lm): scoring side (lm <= 64), unless lm == 0xFFFFFFFF
+    uint32_t pad[2];
+};
+constexpr uint32_t kDictMaxPattern = 1u << 20;  // code points of a query term the wide scan takes (the packed descriptor's field)
 struct DictMatch {  // one matched dictionary term, with what its score needs (search_field.rs:304-321, 691-732)
     uint32_t probe, term;
     uint32_t info;  // optimal-string-alignment distance of the lower-cased hit to the lower-cased term | plain Levenshtein distance << 8 (both
@@ -79,6 +86,9 @@ void launch_scan_union(hipStream_t st, bool with_or, uint32_t total_spans, const
 // all n_probes scan the SAME dictionary image (off / chars); matches are appended to out[0 .. out_cap) (the count keeps running beyond the cap)
 void launch_dict_scan(hipStream_t st, const DictProbe* d_probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const uint16_t* chars, const uint16_t* low_chars,
                       uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out);
+// the same over a 16-bit (char_bytes 2) or 32-bit (char_bytes 4) image, with the probes' queries in `pool`
+void launch_dict_scan_wide(hipStream_t st, uint32_t char_bytes, const DictProbeW* d_probes, const uint32_t* pool, uint32_t probe_base, uint32_t n_probes, const uint32_t* off,
+                           const void* chars, const void* low_chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

@@ -1,8 +1,13 @@
 #!/bin/bash
 # Per-kernel register / scratch / LDS / occupancy report from the compiler (no GPU needed).
+# Every .hip file of the library (SRCS of the Makefile), compiled with the Makefile's flags.  usage: tools/kernel_resources.sh [file.hip ...]
 cd "$(dirname "$0")/../veloci_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -x hip -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-  -Rpass-analysis=kernel-resource-usage -c kernels.hip -o /tmp/kernel_resources.o 2>&1 |
+FLAGS=$(sed -n 's/^CXXFLAGS ?= //p' Makefile)
+FILES=${*:-$(sed -n 's/^SRCS = //p' Makefile | tr ' ' '\n' | grep '\.hip$')}
+OUT=$(mktemp -d)
+for f in $FILES; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -x hip $FLAGS -Rpass-analysis=kernel-resource-usage -c $f -o $OUT/${f%.hip}.o 2>&1
+done |
 python3 -c '
 import re, sys
 cur = None
@@ -16,5 +21,6 @@ for line in sys.stdin:
     elif cur and ":" in t:
         k, v = t.split(":", 1); rows[cur][k.strip()] = v.strip()
 for name, r in rows.items():
-    print("%-70s VGPR %-4s AGPR %-3s SGPR %-4s scratch %-6s occupancy %-3s LDS %s" % (name[:70], r.get("VGPRs"), r.get("AGPRs"), r.get("TotalSGPRs"), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
+    print("%-70s VGPR %-4s AGPR %-3s SGPR %-4s spilled SGPR %-5s scratch %-6s occupancy %-3s LDS %s" % (name[:70], r.get("VGPRs"), r.get("AGPRs"), r.get("TotalSGPRs"), r.get("SGPRs Spill"), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
 '
+rm -rf "$OUT"

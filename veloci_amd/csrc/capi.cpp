@@ -240,6 +240,13 @@ const char* vq_last_error(void) { return g_err.c_str(); }
 const char* vq_version(void) { return "veloci_amd 0.3 (gfx950)"; }
 /* self-check (tests): inputs for which the kernels' fast a/100 differs from the correctly rounded division, over all f16 values */
 uint32_t vq_debug_div100_mismatches(void) { return vq::debug_div100_mismatches(); }
+/* tools/probe_occupancy.py (like the stamp readers below: exported, not part of the header): LDS bytes of a probe kernel's one-wave workgroup (shape: kProbe* of kernels.hpp; nd / na operands beside the cover / probed as arrays; arr_slot words per
+   array operand) and how many of them the runtime keeps resident on a CU */
+uint32_t vq_debug_probe_occupancy(uint32_t shape, uint32_t nd, uint32_t na, uint32_t arr_slot, uint32_t cand_cap, uint32_t* lds_bytes) {
+    const size_t lds = vq::scan_probe_lds_bytes(cand_cap, nd, na, arr_slot);
+    if (lds_bytes) *lds_bytes = uint32_t(lds);
+    return vq::debug_probe_occupancy(shape, lds);
+}
 /* tests, tools: requests that ran a second time because a speculative route's result could not be confirmed (k_scan_probe_or) */
 uint64_t vq_index_speculative_reruns(const vq_index* index) { return index ? index->idx->or_reruns.load() : 0; }
 /* self-check (tests): the facet top-`top` kernels on a caller's histogram */

@@ -753,6 +753,7 @@ struct Compiler {
                 h.d_cov32 = ps.cov32.as<uint32_t>() + uint64_t(ps.pk_start[e.tid]) * 8;
                 h.d_gdir = ps.gdir.as<uint32_t>() + ps.gd_start[e.tid];
                 if (ps.ak_start[e.tid] >= 0) h.d_arr16 = ps.arr16.as<uint16_t>() + uint64_t(ps.ak_start[e.tid]) * 8;
+                h.tile_most = ps.tile_most[e.tid];
             }
             uint32_t li = add_list(h);
             info.cover.push_back(li);
@@ -2299,6 +2300,7 @@ struct Compiler {
                     for (uint32_t k = 0; k < cq.simple_n; ++k) {
                         const HList& l = cq.lists[cq.ops[k].list_begin];
                         cq.probe.leaf[k] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
+                        if ((arr_mask >> k) & 1u) cq.probe_arr_gran = std::max(cq.probe_arr_gran, l.tile_most);
                     }
                 }
                 // ... and with top + skip <= 32 (the candidate buffer is one key per lane, the query has a shared pool) the persistent form of that

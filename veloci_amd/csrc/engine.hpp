@@ -334,6 +334,7 @@ struct PostingStore {  // "<field>.textindex.to_anchor_id_score": padded segment
     std::vector<int64_t> pk_start;      // granule offset of list t inside `cov32`, or -1
     std::vector<int64_t> ak_start;      // granule offset of list t inside `arr16`, or -1 (a tile with more than 2048 entries)
     std::vector<int64_t> gd_start;      // entry offset of list t inside `gdir`
+    std::vector<uint32_t> tile_most;    // most granules list t has in one tile (0 without a tile-packed image): sizes an array operand's LDS slot per launch
     DevBuf cov32, arr16, gdir;
 };
 
@@ -562,6 +563,7 @@ struct HList {
     const uint32_t* d_cov32 = nullptr;  // tile-packed image (PostingStore::cov32 / arr16 / gdir), null without one
     const uint16_t* d_arr16 = nullptr;
     const uint32_t* d_gdir = nullptr;
+    uint32_t tile_most = 0;  // most 8-entry granules of the list in one 32768-doc tile (PostingStore::tile_most)
     int inline_idx = -1;  // >= 0: docs come from inline_lists[inline_idx] (carried inside the blob)
     int inline_val_idx = -1;  // >= 0: f32 values come from inline_vals[inline_val_idx]
 };
@@ -640,6 +642,7 @@ struct CompiledQuery {
     DSimple2 simple2{};  // simple_flags bit 18
     DWide wide{};        // simple_flags bit 24
     DProbe probe{};      // simple_flags bit 25
+    uint32_t probe_arr_gran = 0;  // ... the most granules any of its array operands has in one tile (the launch sizes the operands' LDS slot by it)
     std::vector<DFacet> facets;
     std::vector<FacetOut> facet_out;
     std::map<std::string, std::vector<std::string>> why_found_terms;  // search.rs:186: path -> matched term texts (request.why_found)

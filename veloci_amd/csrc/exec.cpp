@@ -1253,9 +1253,12 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     const size_t up_qmap_f = up_span_f + tbl;
     const size_t up_span_x = up_qmap_f + tbl;   // wide queries (DWide): k_scan_wide
     const size_t up_qmap_x = up_span_x + tbl;
-    const size_t up_span_p = up_qmap_x + tbl;   // ANDs of one id-list cover and bitmap operands: k_scan_probe
-    const size_t up_qmap_p = up_span_p + tbl;
-    const size_t up_qmap_n = up_qmap_p + tbl;   // ... with top + skip <= 32: k_scan_ring (a persistent grid: no span table, (query, span) items instead)
+    // ANDs (ORs) of one id-list cover and bitmap / array operands: k_scan_probe_*, a kernel per shape class with a table of its own.  The classes'
+    // tables lie one behind the other (class c: its queries + the closing entry of its span table), so all of them take one table's room + kProbeShapes entries
+    const size_t tbl_p = align_up(size_t(nq + 1 + kProbeShapes) * 4, 256);
+    const size_t up_span_p = up_qmap_x + tbl;
+    const size_t up_qmap_p = up_span_p + tbl_p;
+    const size_t up_qmap_n = up_qmap_p + tbl_p;   // ... with top + skip <= 32: k_scan_ring (a persistent grid: no span table, (query, span) items instead)
     const size_t up_work_n = up_qmap_n + tbl;   // its item counter and error word (zeroed with every upload)
     size_t ring_items_max = 0;                  // its item table: only when the launch's queries differ in their span counts
     for (size_t i = 0; i < n; ++i)
@@ -1274,8 +1277,20 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     bool facets_rich = false;
     uint32_t n_leaf = 0, spans_leaf = 0;
     uint32_t n_xwide = 0, spans_xwide = 0, leaves_xwide = 0, scatter_xwide = 0;
-    uint32_t n_probe = 0, spans_probe = 0, nd_probe = 1;
-    bool probe_any_and = false, probe_any_or = false;
+    struct ProbeClass {
+        uint32_t first = 0, n = 0, spans = 0;  // first: where the class's tables start inside the probe tables
+        uint32_t na_seen = 0, arr_slot = 0;    // bit NA: a query with NA array operands; words of an array operand's LDS slot (the fullest tile of the class's array lists)
+    } pcls[kProbeShapes];
+    auto probe_class = [](const CompiledQuery& cq) -> uint32_t {
+        if ((cq.simple_flags >> 27) & 1u) return kProbeOr;
+        const uint32_t nd = cq.simple_n - 1, na = uint32_t(__builtin_popcount((cq.simple_flags >> 12) & 0xFu));
+        return nd <= 1 ? kProbeAnd1 : nd == 2 ? kProbeAnd2A0 + na : kProbeAnd3A0 + na;
+    };
+    auto on_probe = [](const CompiledQuery& cq) {  // what the routing below may send to k_scan_probe_* (never fewer queries than it does: the tables are sized by this)
+        return cq.status == 0 && ((cq.simple_flags >> 25) & 1u) && !((cq.simple_flags >> 26) & 1u) && !((cq.simple_flags >> 19) & 1u) && !((cq.simple_flags >> 24) & 1u) &&
+               !((cq.simple_flags >> 18) & 1u);
+    };
+    bool any_probe = false;
     uint32_t n_ring = 0, items_ring = 0, nd_ring = 1, ring_spans_each = 0;
     uint64_t cls_layout[K_COUNT_] = {}, cls_algo[K_COUNT_] = {}, cls_q[K_COUNT_] = {};
     {
@@ -1308,9 +1323,19 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
         uint32_t accf = 0, accx = 0;
         uint32_t* sx = reinterpret_cast<uint32_t*>(hup + up_span_x);
         uint32_t* mx = reinterpret_cast<uint32_t*>(hup + up_qmap_x);
-        uint32_t accg = 0, accs = 0, accd = 0, accw = 0, accr = 0, accp = 0;
+        uint32_t accg = 0, accs = 0, accd = 0, accw = 0, accr = 0;
         uint32_t* sp = reinterpret_cast<uint32_t*>(hup + up_span_p);
         uint32_t* mp = reinterpret_cast<uint32_t*>(hup + up_qmap_p);
+        {  // how many queries every probe class holds: where its tables start
+            uint32_t cnt[kProbeShapes] = {};
+            for (size_t i = 0; i < n; ++i)
+                if (on_probe(pb->queries[i])) ++cnt[probe_class(pb->queries[i])];
+            uint32_t at = 0;
+            for (uint32_t c = 0; c < kProbeShapes; ++c) {
+                pcls[c].first = at;
+                at += cnt[c] + 1;
+            }
+        }
         uint32_t* mn = reinterpret_cast<uint32_t*>(hup + up_qmap_n);
         uint32_t ring_max_spans = 0;
         std::vector<uint32_t> ring_ns;  // spans of k_scan_ring's queries
@@ -1363,11 +1388,14 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
                 items_ring += cq.n_spans;
             } else if ((cq.simple_flags >> 25) & 1u) {
                 kclass = K_SCAN_PROBE;
-                ((cq.simple_flags >> 27) & 1u ? probe_any_or : probe_any_and) = true;
-                nd_probe = std::max<uint32_t>(nd_probe, cq.simple_n - 1);
-                sp[n_probe] = accp;
-                mp[n_probe++] = qi;
-                accp += cq.n_spans;
+                if (!on_probe(cq)) throw VelociError(ERR_DEVICE, "probe query outside the probe tables (internal)");
+                ProbeClass& pc = pcls[probe_class(cq)];
+                pc.na_seen |= 1u << uint32_t(__builtin_popcount((cq.simple_flags >> 12) & 0xFu));
+                pc.arr_slot = std::max(pc.arr_slot, cq.probe_arr_gran * 4u);
+                sp[pc.first + pc.n] = pc.spans;
+                mp[pc.first + pc.n++] = qi;
+                pc.spans += cq.n_spans;
+                any_probe = true;
             } else if (cq.simple_flags && cq.simple_n > 1 && cq.ops.back().kind == OP_AND) {
                 kclass = K_SCAN_AND;
                 scatter_wide = std::max<uint32_t>(scatter_wide, cq.simple_n - uint32_t(__builtin_popcount(cq.simple_flags & 0xFu)));
@@ -1402,8 +1430,7 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
         spans_leaf = accf;
         sx[n_xwide] = accx;
         spans_xwide = accx;
-        sp[n_probe] = accp;
-        spans_probe = accp;
+        for (const ProbeClass& pc : pcls) sp[pc.first + pc.n] = pc.spans;
         if (n_ring) {  // k_scan_ring's items in round-major order: span 0 of every query, then span 1, ... (a query's pool is warm after its first span)
             if (ring_uniform) ring_spans_each = ring_max_spans;
             else {
@@ -1493,9 +1520,17 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
                          reinterpret_cast<uint32_t*>(dup + up_work_n), keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_probe) {
+    if (any_probe) {  // (one timer over the shape kernels: the profile class is the sum of them)
         LaunchTimer t(prof, ws, st, K_SCAN_PROBE, cls_layout[K_SCAN_PROBE], cls_algo[K_SCAN_PROBE], cls_q[K_SCAN_PROBE]);
-        launch_scan_probe(st, nd_probe, spans_probe, pb->d_blobs, pb->d_blob_off, tab(up_span_p), tab(up_qmap_p), n_probe, cand_cap, keys_ptr, hits_ptr, probe_any_and, probe_any_or);
+        static const bool trace = std::getenv("VQ_PROBE_TRACE") != nullptr;  // tools: what every shape kernel of a launch was given
+        for (uint32_t c = 0; c < kProbeShapes; ++c)
+            if (pcls[c].spans && trace)
+                std::fprintf(stderr, "probe launch: shape %u, %u queries, %u spans, array slot %u words (fullest tile: %u granules), NA seen 0x%x\n", c, pcls[c].n, pcls[c].spans,
+                             pcls[c].arr_slot, pcls[c].arr_slot / 4, pcls[c].na_seen);
+        for (uint32_t c = 0; c < kProbeShapes; ++c)
+            if (pcls[c].spans)
+                launch_scan_probe_shape(st, c, pcls[c].na_seen, pcls[c].arr_slot, pcls[c].spans, pb->d_blobs, pb->d_blob_off, tab(up_span_p) + pcls[c].first, tab(up_qmap_p) + pcls[c].first,
+                                        pcls[c].n, cand_cap, keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
     if (spans_wide) {

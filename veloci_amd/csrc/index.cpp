@@ -329,6 +329,7 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         ps.pk_start.assign(ps.num_tokens, -1);
         ps.ak_start.assign(ps.num_tokens, -1);
         ps.gd_start.assign(ps.num_tokens, -1);
+        ps.tile_most.assign(ps.num_tokens, 0);
         {
             const uint64_t ptiles = (idx->bitmap_words >> (kProbeTileShift - 5)) + 2;  // (entry `one behind the last tile` included)
             uint64_t cov_gran = 0, arr_gran = 0;
@@ -358,6 +359,7 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
                 ps.gd_start[t] = int64_t(j * (ptiles + 1));
                 if (gran_of[j] >= (1ull << 28)) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "posting list too long for its tile-packed image");
                 ps.pk_start[t] = int64_t(cov_gran);
+                ps.tile_most[t] = most_of[j];
                 cov_gran += gran_of[j];
                 if (most_of[j] <= 256) {  // no tile holds more than 2048 entries: the list can be an array operand
                     ps.ak_start[t] = int64_t(arr_gran);

@@ -59,9 +59,12 @@ uint32_t debug_div100_mismatches();
 int debug_facet_select(const uint32_t* hist_host, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_vals_host, uint32_t* out_counts_host);
 void launch_scan_simple(hipStream_t st, bool wide, uint32_t n_scatter, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off, const uint32_t* span_base,
                         const uint32_t* qmap, uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits, uint32_t* hist, bool facet_cache = false);
-size_t scan_probe_lds_bytes(uint32_t cand_cap, uint32_t nd);
-void launch_scan_probe(hipStream_t st, uint32_t max_nd, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off, const uint32_t* span_base, const uint32_t* qmap,
-                       uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits, bool any_and = true, bool any_or = false);
+// k_scan_probe_* (scan_probe.hip): one kernel per shape class, each launched over a (span_base, qmap) table of its own
+enum : uint32_t { kProbeAnd1 = 0, kProbeAnd2A0, kProbeAnd2A1, kProbeAnd2A2, kProbeAnd3A0, kProbeAnd3A1, kProbeAnd3A2, kProbeAnd3A3, kProbeOr, kProbeShapes };  // AND of ND operands beside the cover (ND >= 2: per number of array operands) / OR
+size_t scan_probe_lds_bytes(uint32_t cand_cap, uint32_t nd, uint32_t na, uint32_t arr_slot);
+uint32_t debug_probe_occupancy(uint32_t shape, size_t lds_bytes);
+void launch_scan_probe_shape(hipStream_t st, uint32_t shape, uint32_t na_seen, uint32_t arr_slot, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off,
+                             const uint32_t* span_base, const uint32_t* qmap, uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits);
 // k_scan_ring (scan_ring.hip): persistent loader / consumer form of k_scan_probe.  `work`: two zeroed u32 (item counter, error word)
 uint32_t scan_ring_consumers(uint32_t max_nd);
 uint32_t scan_ring_slots(uint32_t maxnd, uint32_t consumers);

@@ -72,20 +72,27 @@ void debug_read_probe_stamps(unsigned long long* out, int reset) {
 #endif
 
 constexpr uint32_t kPMaxR = 2;                  // rounds of 256 cover postings of a tile that are prefetched into registers (more: fetched on the spot)
-constexpr uint32_t kPU = 64 + kPMaxR * 256;     // unranked queue: live hits of the current tile, (doc - tile_lo) << 16 | raw f16 score of the cover
+constexpr uint32_t kPU = 256;                   // unranked queue: live hits of the current tile, (doc - tile_lo) << 16 | raw f16 score of the cover.  One round's
+                                                // worth: a round that would not fit behind what is queued drains the queue first (probe_eval)
+static_assert(kPU >= 256, "a round of 256 postings must fit the empty queue");
 constexpr uint32_t kPR = 128;                   // ranked queue
-// LDS map (u32): misc[8] | shape[32] | uq[kPU] | rdoc[kPR] rraw[kPR] ridx[ND][kPR] | tile[ND][kPTW] | rank[ND][kPRk] | cand[2 * cand_cap]
-// (the candidate buffer, the only part sized at run time, comes last: every other offset is a constant of the instantiation)
+// LDS map (u32): misc[8] | shape[24] | uq[kPU] | rdoc[kPR] rraw[kPR] ridx[ND][kPR] | tile[NB][kPTW] | rank[NB][kPRk] | arr[NA][arr_slot] | cand[2 * cand_cap]
+// Areas are sized by role: a bitmap operand has its 1024 words and 64 rank entries, an array operand a slot of `arr_slot` words — what the
+// fullest tile of the launch's array lists takes (PostingStore::tile_most; a granule of 8 offsets is 4 words), at most kPTW.  The parts sized at
+// run time come last: every other offset is a constant of the instantiation.  The headline shape <2, 1> stays below 10240 B — sixteen
+// one-wave workgroups per CU — as long as no tile of its array list holds more than about 1200 postings.
 constexpr uint32_t kPLdsShape = 8;
-constexpr uint32_t kPLdsU = kPLdsShape + 32;
+constexpr uint32_t kPLdsU = kPLdsShape + 24;  // (the shape words end at kShScores + 2 * 3 = 18)
 constexpr uint32_t kPLdsR = kPLdsU + kPU;
 __host__ __device__ constexpr uint32_t probe_lds_tile(uint32_t nd) { return kPLdsR + (2 + nd) * kPR; }
-__host__ __device__ constexpr uint32_t probe_lds_cand(uint32_t nd) { return probe_lds_tile(nd) + nd * (kPTW + kPRk); }
-size_t scan_probe_lds_bytes(uint32_t cand_cap, uint32_t nd) { return (size_t)(probe_lds_cand(nd) + 2 * cand_cap) * 4 + 16; }
+__host__ __device__ constexpr uint32_t probe_lds_arr(uint32_t nd, uint32_t nb) { return probe_lds_tile(nd) + nb * (kPTW + kPRk); }
+size_t scan_probe_lds_bytes(uint32_t cand_cap, uint32_t nd, uint32_t na, uint32_t arr_slot) {
+    return (size_t)(probe_lds_arr(nd, nd - na) + na * arr_slot + 2 * cand_cap) * 4 + 16;
+}
 
 // OR: the root is an OR of leaves with a term slot each (set_op.rs:87-220) — see the kernel's comment
 template <uint32_t ND, uint32_t NA, bool OR = false>  // ND operands beside the cover, the last NA of them (roles NB .. ND-1) probed as 16-bit arrays
-__device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, const uint32_t span, const uint32_t q, const uint32_t cand_cap,
+__device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, const uint32_t span, const uint32_t q, const uint32_t cand_cap, const uint32_t arr_slot,
                                            unsigned long long* __restrict__ span_keys, unsigned long long* __restrict__ num_hits) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -105,9 +112,10 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
     uint32_t* sh = lds + kPLdsShape;
     uint32_t* uq = lds + kPLdsU;
     uint32_t* rq = lds + kPLdsR;  // rdoc[kPR] rraw[kPR] ridx[ND][kPR]
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(lds + probe_lds_cand(ND));
-    uint32_t* tile = lds + probe_lds_tile(ND);  // [ND][kPTW]: a bitmap operand's 1024 words / an array operand's (up to) 2048 16-bit offsets
-    uint32_t* rank = tile + ND * kPTW;          // [ND][kPRk] (bitmap operands only)
+    uint32_t* tile = lds + probe_lds_tile(ND);   // [NB][kPTW]: a bitmap operand's 1024 words
+    uint32_t* rank = tile + NB * kPTW;           // [NB][kPRk]
+    uint32_t* arr = lds + probe_lds_arr(ND, NB);  // [NA][arr_slot]: an array operand's 16-bit offsets of the tile (arr_slot: a multiple of 4 words, the launch's fullest tile)
+    unsigned long long* cand = reinterpret_cast<unsigned long long*>(arr + NA * arr_slot);
     unsigned long long* const gthr = reinterpret_cast<unsigned long long*>(const_cast<uint8_t*>(blob) + offsetof(QHeader, gthr));
     CandState cs{cand, cand_n, thr, cand_cap, gthr};
     cs.upper = H->key_upper;
@@ -450,7 +458,7 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             const uint32_t rel = e >> 16;
 #pragma unroll
             for (uint32_t a = 0; a < NA; ++a) {
-                const uint16_t* A = reinterpret_cast<const uint16_t*>(tile + (NB + a) * kPTW);
+                const uint16_t* A = reinterpret_cast<const uint16_t*>(arr + a * arr_slot);
                 uint32_t lo = 0u, len = a_cnt[a];  // uniform length: every lane takes the same number of steps
 #ifdef VQ_PROBE_NO_SEARCH  // diagnostic build (wrong results): what the kernel takes without the lookups' dependent reads
                 lo = rel & 7u;
@@ -511,7 +519,8 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
         }
         return pw;
     };
-    auto probe_eval = [&](const u32x4 e4, const ProbeWords& pw) {
+    // may_overflow: something of the tile may be queued already (every round but a tile's first)
+    auto probe_eval = [&](const u32x4 e4, const ProbeWords& pw, const bool may_overflow) {
         const uint32_t ee[4] = {e4.x, e4.y, e4.z, e4.w};
         unsigned long long lm[4];
         bool live[4];
@@ -546,6 +555,10 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             }
         }
         if (lm[0] | lm[1] | lm[2] | lm[3]) {  // uniform
+            if (may_overflow) {  // the queue holds one round: what does not fit behind the entries of earlier rounds waits until those are ranked (the tile is in LDS, the round in registers)
+                const uint32_t add = (uint32_t)__popcll(lm[0]) + (uint32_t)__popcll(lm[1]) + (uint32_t)__popcll(lm[2]) + (uint32_t)__popcll(lm[3]);
+                while (un + add > kPU) rank_some(un < 64u ? un : 64u);  // uniform; a dense stretch of hits only
+            }
 #pragma unroll
             for (uint32_t c = 0; c < 4; ++c) {
                 if (live[c]) uq[un + (uint32_t)__popcll(lm[c] & ((1ull << lane) - 1ull))] = ee[c];  // (in-tile offset << 16 | raw score: the packed word itself)
@@ -595,7 +608,7 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             for (uint32_t a = 0; a < NA; ++a) {
 #pragma unroll
                 for (uint32_t h = 0; h < kPNV; ++h)
-                    if (h * 64u < na_nv[a]) reinterpret_cast<u32x4*>(tile + (NB + a) * kPTW)[h * 64u + lane] = wk[NB + a][h];  // uniform: only the vectors that hold entries of the tile
+                    if (h * 64u + lane < na_nv[a]) reinterpret_cast<u32x4*>(arr + a * arr_slot)[h * 64u + lane] = wk[NB + a][h];  // only the lanes that hold entries of the tile (the slot ends with the launch's fullest one)
                 a_g0[a] = na_g0[a];
                 a_cnt[a] = na_nv[a] * 8u;
             }
@@ -669,17 +682,16 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
                 for (uint32_t r = 0; r < kPMaxR; ++r)
                     if (r < rounds) {  // uniform
                         PS_COUNT(9)
-                        probe_eval(cid[r], pw[r]);
+                        probe_eval(cid[r], pw[r], r > 0u);
                     }
             }
             for (uint32_t r = kPMaxR; r < rounds; ++r) {  // a dense stretch of the cover: further rounds are fetched on the spot
-                while (un >= kPU - 256u) rank_some(64u);  // uniform: room for another round
                 const uint32_t v = v0 + r * 64u + lane;
                 u32x4 e4 = kSent;
                 if (v < v1) e4 = cc4[v];
                 PS_COUNT(9)
                 const ProbeWords pw = probe_read(e4);
-                probe_eval(e4, pw);
+                probe_eval(e4, pw, true);
             }
             PS_AT(2)
             while (un) {  // uniform: the tile's queued postings are looked up / ranked while its words are still in LDS
@@ -710,7 +722,8 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
     PS_FLUSH
 }
 
-// which (query, span) a workgroup of the launch runs
+// which (query, span) a workgroup of the launch runs: every kernel below has a table of its own (span_base: prefix sums of the spans of ITS queries,
+// qmap: their blob slots), so no workgroup starts only to find that its query is another kernel's
 __device__ __forceinline__ void probe_item(const uint32_t* __restrict__ span_base, const uint32_t* __restrict__ qmap, uint32_t nq, uint32_t* q, uint32_t* span) {
     uint32_t lo = 0, hi = nq;
     const uint32_t wg = blockIdx.x;
@@ -723,29 +736,56 @@ __device__ __forceinline__ void probe_item(const uint32_t* __restrict__ span_bas
     *q = qmap[lo];
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_scan_probe(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ blob_off,
-                                                                                               const uint32_t* __restrict__ span_base, const uint32_t* __restrict__ qmap, uint32_t nq,
-                                                                                               uint32_t cand_cap, unsigned long long* __restrict__ span_keys,
-                                                                                               unsigned long long* __restrict__ num_hits) {
-    uint32_t q, span;
-    probe_item(span_base, qmap, nq, &q, &span);
+// One kernel per shape: a kernel is charged the registers of the largest body it CONTAINS, whether a launch runs that body or not (all nine
+// AND bodies in one kernel: 166 VGPRs, three waves per SIMD, for a headline body that needs 128).  ND = 2 — the headline is <2, 1> — has a
+// kernel per NA, and so has ND = 3 (its four bodies in one kernel at three waves: 12 B of scratch per lane); ND = 1 keeps the NA switch inside,
+// both bodies lie well below the 128-register line.  waves_per_eu is the most each kernel's bodies reach without scratch: 4 for ND <= 2, 3
+// for ND = 3 (<3, 1> forced to 4 spills 76 B per lane) and for the OR.
+// tests/test_kernel_resources.py holds the compiler's report against that.
+#define VQ_PROBE_PARAMS                                                                                                                                       \
+    const uint8_t *__restrict__ blobs, const uint32_t *__restrict__ blob_off, const uint32_t *__restrict__ span_base, const uint32_t *__restrict__ qmap, uint32_t nq, \
+        uint32_t cand_cap, uint32_t arr_slot, unsigned long long *__restrict__ span_keys, unsigned long long *__restrict__ num_hits
+#define VQ_PROBE_ITEM                           \
+    uint32_t q, span;                           \
+    probe_item(span_base, qmap, nq, &q, &span); \
     const uint8_t* blob = blobs + blob_off[q];
-    const uint32_t n = as_const<QHeader>(blob)->simple_n;
-    if ((as_const<QHeader>(blob)->simple_flags >> 27) & 1u) return;  // an OR: k_scan_probe_or's (same grid)
-    const uint32_t na = (uint32_t)__popc((as_const<QHeader>(blob)->simple_flags >> 12) & 0xFu);  // operands probed as 16-bit arrays
-    if (n == 2u) {
-        if (na == 0u) probe_body<1, 0>(blob, span, q, cand_cap, span_keys, num_hits);
-        else probe_body<1, 1>(blob, span, q, cand_cap, span_keys, num_hits);
-    } else if (n == 3u) {
-        if (na == 0u) probe_body<2, 0>(blob, span, q, cand_cap, span_keys, num_hits);
-        else if (na == 1u) probe_body<2, 1>(blob, span, q, cand_cap, span_keys, num_hits);
-        else probe_body<2, 2>(blob, span, q, cand_cap, span_keys, num_hits);
-    } else {
-        if (na == 0u) probe_body<3, 0>(blob, span, q, cand_cap, span_keys, num_hits);
-        else if (na == 1u) probe_body<3, 1>(blob, span, q, cand_cap, span_keys, num_hits);
-        else if (na == 2u) probe_body<3, 2>(blob, span, q, cand_cap, span_keys, num_hits);
-        else probe_body<3, 3>(blob, span, q, cand_cap, span_keys, num_hits);
-    }
+#ifndef VQ_PROBE_WAVES  // experiment builds (make variant DEFS=-DVQ_PROBE_WAVES=3): the waves_per_eu minimum of the ND <= 2 kernels
+#define VQ_PROBE_WAVES 4
+#endif
+#define VQ_PROBE_KERNEL(waves) __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves, 8))) void
+
+VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_1(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    if (((as_const<QHeader>(blob)->simple_flags >> 12) & 0xFu) == 0u) probe_body<1, 0>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+    else probe_body<1, 1>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_2_0(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<2, 0>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_2_1(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<2, 1>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_2_2(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<2, 2>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(3) k_scan_probe_3_0(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<3, 0>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(3) k_scan_probe_3_1(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<3, 1>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(3) k_scan_probe_3_2(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<3, 2>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+}
+VQ_PROBE_KERNEL(3) k_scan_probe_3_3(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    probe_body<3, 3>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
 }
 
 // The OR form of the same scan (simple_flags bit 27): an OR of 2 or 3 leaves with a term slot each whose sparsest operand streams as the cover
@@ -754,28 +794,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
 // WITHOUT the cover are counted, never scored: exact as long as none of them can reach the request's k-th best score — their scores are
 // bounded by the OR formula on the operands' list maxima (CompiledQuery::or_skip_bound), and the host checks the k-th key of the finished
 // request against that bound (finish_batch), running the request again on k_scan_simple when the check fails (an OR whose best hits lack
-// its rarest term).  Its own kernel: its register needs are not the AND's.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_scan_probe_or(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ blob_off,
-                                                                                                  const uint32_t* __restrict__ span_base, const uint32_t* __restrict__ qmap, uint32_t nq,
-                                                                                                  uint32_t cand_cap, unsigned long long* __restrict__ span_keys,
-                                                                                                  unsigned long long* __restrict__ num_hits) {
-    uint32_t q, span;
-    probe_item(span_base, qmap, nq, &q, &span);
-    const uint8_t* blob = blobs + blob_off[q];
-    const uint32_t n = as_const<QHeader>(blob)->simple_n;
-    if (!((as_const<QHeader>(blob)->simple_flags >> 27) & 1u)) return;
-    if (n == 2u) probe_body<1, 0, true>(blob, span, q, cand_cap, span_keys, num_hits);
-    else probe_body<2, 0, true>(blob, span, q, cand_cap, span_keys, num_hits);  // (compile.cpp sends ORs of 2 or 3 leaves: a fourth operand's eight bounds spill)
+// its rarest term).
+VQ_PROBE_KERNEL(3) k_scan_probe_or(VQ_PROBE_PARAMS) {
+    VQ_PROBE_ITEM
+    if (as_const<QHeader>(blob)->simple_n == 2u) probe_body<1, 0, true>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+    else probe_body<2, 0, true>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);  // (compile.cpp sends ORs of 2 or 3 leaves: a fourth operand's eight bounds spill)
 }
 
-// max_nd: most dense operands of a query of the launch (sizes the LDS tile area); any_and / any_or: which kinds of query the launch holds
-void launch_scan_probe(hipStream_t st, uint32_t max_nd, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off, const uint32_t* span_base, const uint32_t* qmap,
-                       uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits, bool any_and, bool any_or) {
+static auto* probe_kernel(uint32_t shape) {
+    return shape == kProbeAnd1 ? k_scan_probe_1 : shape == kProbeAnd2A0 ? k_scan_probe_2_0 : shape == kProbeAnd2A1 ? k_scan_probe_2_1 : shape == kProbeAnd2A2 ? k_scan_probe_2_2 :
+           shape == kProbeAnd3A0 ? k_scan_probe_3_0 : shape == kProbeAnd3A1 ? k_scan_probe_3_1 : shape == kProbeAnd3A2 ? k_scan_probe_3_2 : shape == kProbeAnd3A3 ? k_scan_probe_3_3 :
+                                                                                                                                                                    k_scan_probe_or;
+}
+
+// tools, DESIGN.md §5: one-wave workgroups of a shape's kernel that the runtime keeps resident on a CU with `lds_bytes` of LDS each (0: the query failed)
+uint32_t debug_probe_occupancy(uint32_t shape, size_t lds_bytes) {
+    int n = 0;
+    if (shape >= kProbeShapes || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, probe_kernel(shape), 64, lds_bytes) != hipSuccess || n < 0) return 0;
+    return (uint32_t)n;
+}
+
+// One launch over the table of one shape class (kProbe*: kernels.hpp).  na_seen: bit NA is set when a query of the table probes NA operands as
+// arrays; arr_slot: words of an array operand's LDS slot (the fullest tile among the table's array lists).  The LDS is what the largest
+// instantiation among the table's queries takes.
+void launch_scan_probe_shape(hipStream_t st, uint32_t shape, uint32_t na_seen, uint32_t arr_slot, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off,
+                             const uint32_t* span_base, const uint32_t* qmap, uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits) {
     if (!total_spans) return;
-    if (any_and)
-        hipLaunchKernelGGL(k_scan_probe, dim3(total_spans), dim3(64), scan_probe_lds_bytes(cand_cap, max_nd), st, blobs, blob_off, span_base, qmap, nq, cand_cap, span_keys, num_hits);
-    if (any_or)
-        hipLaunchKernelGGL(k_scan_probe_or, dim3(total_spans), dim3(64), scan_probe_lds_bytes(cand_cap, max_nd), st, blobs, blob_off, span_base, qmap, nq, cand_cap, span_keys, num_hits);
+    const uint32_t nd = shape == kProbeAnd1 ? 1u : (shape >= kProbeAnd3A0 && shape <= kProbeAnd3A3) ? 3u : 2u;  // (the OR kernel: up to two bitmap operands)
+    size_t lds = 0;
+    for (uint32_t na = 0; na <= nd; ++na)
+        if ((na_seen >> na) & 1u) lds = std::max(lds, scan_probe_lds_bytes(cand_cap, nd, na, arr_slot));
+    hipLaunchKernelGGL(probe_kernel(shape), dim3(total_spans), dim3(64), lds, st, blobs, blob_off, span_base, qmap, nq, cand_cap, arr_slot, span_keys, num_hits);
 }
 
 }  // namespace vq

@@ -39,7 +39,7 @@ static bool timing_enabled() {
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_union<count>", "k_union<write>", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
+const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
                                             "k_scan_simple<2,rich>", "k_scan_ring (AND)", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
                                             "k_merge_spans", "k_finalize", "k_facet_select", "k_locality", "k_boost1n"};
 
@@ -386,6 +386,7 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
 
 // K2: run the union jobs of a batch.  Level 1 merges groups of <= 64 posting lists (one lane per list); a job with
 // more lists gets a level-2 task over the level-1 outputs.  Each level: count pass -> host prefix sums -> write pass.
+// A job with more lists than two levels take (VQ_UNION_DENSE_MIN, 4096) goes to the dense route instead (run_union_dense).
 namespace {
 struct UnionTaskH {
     std::vector<UList> lists;
@@ -546,10 +547,150 @@ void run_range_jobs(const Index& idx, Workspace& ws, RangeTable& table, const Un
     }
 }
 
+// K2 for wide leaves (union_dense.hip): a u32 key per doc of the shard's range in a slab, raised by one atomic max per posting, then compacted
+// into k_union<write>'s output format.  The jobs run in groups whose slabs fit the budget; nothing comes back to the host between the
+// launches, the lengths and largest values of all jobs are fetched in one read-back at the end.  A job's output slice is sized by its upper
+// bound, min(postings, docs of the range).
+namespace {
+size_t union_dense_min() {  // jobs with more lists than this take the dense route
+    static const size_t v = [] {
+        const char* e = std::getenv("VQ_UNION_DENSE_MIN");
+        return size_t(std::min<long long>(std::max<long long>(e ? std::atoll(e) : 64 * 64, 1), 64 * 64));  // (two levels of k_union take no more than 64 x 64)
+    }();
+    return v;
+}
+uint64_t union_dense_slab_budget() {  // bytes of slabs alive at once (a job always gets one)
+    static const uint64_t v = [] {
+        const char* e = std::getenv("VQ_UNION_DENSE_SLAB_MB");
+        return uint64_t(std::min<long long>(std::max<long long>(e ? std::atoll(e) : 1024, 0), 1ll << 20)) << 20;
+    }();
+    return v;
+}
+
+void run_union_dense(const Index& idx, Workspace& ws, const std::vector<UnionJob*>& jobs, hipStream_t st) {
+    if (jobs.empty()) return;
+    const uint32_t range = idx.doc_hi - idx.doc_lo;
+    const uint32_t job_blocks = std::max<uint32_t>(uint32_t((uint64_t(range) + kDenseBlockDocs - 1) / kDenseBlockDocs), 1u);
+    const uint64_t slab_words = uint64_t(job_blocks) * kDenseBlockDocs;
+    const size_t per_group = size_t(std::min<uint64_t>(std::max<uint64_t>(union_dense_slab_budget() / (slab_words * 4), 1), jobs.size()));
+    struct Group {
+        size_t job_begin, n_jobs, list_begin, n_lists;
+        uint64_t postings;
+    };
+    std::vector<Group> groups;
+    std::vector<UDenseList> lists;
+    std::vector<UDenseJob> djobs(jobs.size());
+    std::vector<uint64_t> cap(jobs.size());
+    uint64_t out_cursor = 0;
+    for (size_t jb = 0; jb < jobs.size(); jb += per_group) {
+        Group g{jb, std::min(per_group, jobs.size() - jb), lists.size(), 0, 0};
+        for (size_t k = 0; k < g.n_jobs; ++k) {
+            UDenseJob& d = djobs[jb + k];
+            d.slab_off = k * slab_words;
+            d.out_off = out_cursor;
+            d.block_begin = uint32_t(k) * job_blocks;
+            d.n_blocks = job_blocks;
+            d.result = uint32_t(jb + k);
+            d.pad = 0;
+            const uint64_t before = g.postings;
+            for (auto& t : jobs[jb + k]->terms) {
+                const PostingStore& ps = *t.store;
+                if (!ps.len[t.token]) continue;  // (a shard without postings of the term)
+                UDenseList u{};
+                u.docs = ps.docs.as<uint32_t>() + ps.start[t.token];
+                u.scores = ps.scores.as<uint16_t>() + ps.start[t.token];
+                u.first = g.postings;
+                u.term_score = t.score;
+                u.job = uint32_t(k);
+                lists.push_back(u);
+                g.postings += ps.len[t.token];
+            }
+            cap[jb + k] = std::min<uint64_t>(g.postings - before, range);
+            out_cursor += (cap[jb + k] + 8 + 3) / 4 * 4;  // 8 sentinel entries behind every list, starts stay 16-byte aligned
+        }
+        g.n_lists = lists.size() - g.list_begin;
+        if (g.n_lists > 0xFFFFFFF0ull) throw VelociError(ERR_UNSUPPORTED, "leaf expansions of one batch with more than 2^32 posting lists");
+        UDenseList end{};
+        end.first = g.postings;
+        lists.push_back(end);
+        groups.push_back(g);
+    }
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_jobs = al(lists.size() * sizeof(UDenseList)), o_res = o_jobs + al(djobs.size() * sizeof(UDenseJob)), o_cnt = o_res + al(jobs.size() * sizeof(UDenseResult)),
+                 o_max = o_cnt + al(per_group * size_t(job_blocks) * 4), bytes = o_max + al(per_group * size_t(job_blocks) * 4);
+    ws.d_union_dense_meta.ensure(bytes);
+    ws.d_union_slab.ensure(per_group * slab_words * 4);
+    ws.d_union_dense_docs.ensure(out_cursor * 4 + 64);
+    ws.d_union_dense_vals.ensure(out_cursor * 4 + 64);
+    uint8_t* m = ws.d_union_dense_meta.as<uint8_t>();
+    const UDenseList* d_lists = reinterpret_cast<const UDenseList*>(m);
+    const UDenseJob* d_jobs = reinterpret_cast<const UDenseJob*>(m + o_jobs);
+    UDenseResult* d_res = reinterpret_cast<UDenseResult*>(m + o_res);
+    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(m + o_cnt);
+    uint32_t* d_max = reinterpret_cast<uint32_t*>(m + o_max);
+    uint32_t* slab = ws.d_union_slab.as<uint32_t>();
+    VQ_HIP(hipMemcpyAsync(m, lists.data(), lists.size() * sizeof(UDenseList), hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(m + o_jobs, djobs.data(), djobs.size() * sizeof(UDenseJob), hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemsetAsync(d_res, 0, jobs.size() * sizeof(UDenseResult), st));  // (a group without postings launches no scatter; its lists are empty all the same)
+    const bool timed = idx.profile.enabled;
+    std::vector<std::pair<size_t, size_t>> write_slots;  // (timed launch, group): the write pass's output bytes are known after the read-back
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const Group& g = groups[gi];
+        const uint32_t n_blocks = uint32_t(g.n_jobs) * job_blocks;
+        const uint64_t slab_bytes = g.n_jobs * slab_words * 4;
+        {  // slab clear + scatter: 4 B per doc written, 6 B per posting read, one 4-byte atomic per posting
+            LaunchTimer timer(timed, ws, st, K_UNION_DENSE_SCATTER, slab_bytes + g.postings * 10, g.postings * 6, g.n_jobs);
+            VQ_HIP(hipMemsetAsync(slab, 0, slab_bytes, st));
+            launch_union_dense_scatter(st, d_lists + g.list_begin, uint32_t(g.n_lists), g.postings, d_jobs + g.job_begin, slab, idx.doc_lo, range);
+            VQ_HIP(hipGetLastError());
+        }
+        {  // 4 B per doc read; a count and a largest key per block written, read again by the prefix sums, the offsets written
+            LaunchTimer timer(timed, ws, st, K_UNION_DENSE_COUNT, slab_bytes + uint64_t(n_blocks) * 20, slab_bytes, g.n_jobs);
+            launch_union_dense_count(st, d_jobs + g.job_begin, uint32_t(g.n_jobs), n_blocks, slab, d_cnt, d_max, d_res);
+            VQ_HIP(hipGetLastError());
+        }
+        {  // 4 B per doc read, 8 B per entry written (added below)
+            LaunchTimer timer(timed, ws, st, K_UNION_DENSE_WRITE, slab_bytes + uint64_t(n_blocks) * 4, slab_bytes, g.n_jobs);
+            if (timer.ws) write_slots.push_back({timer.slot, gi});
+            launch_union_dense_write(st, d_jobs + g.job_begin, uint32_t(g.n_jobs), n_blocks, slab, d_cnt, idx.doc_lo, ws.d_union_dense_docs.as<uint32_t>(),
+                                     ws.d_union_dense_vals.as<float>());
+            VQ_HIP(hipGetLastError());
+        }
+    }
+    std::vector<UDenseResult> res(jobs.size());
+    VQ_HIP(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(UDenseResult), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipStreamSynchronize(st));
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        if (res[j].len > cap[j]) throw VelociError(ERR_DEVICE, "dense union wrote more entries than its postings (internal)");
+        if (res[j].len > 0xFFFFFFF0u) throw VelociError(ERR_UNSUPPORTED, "materialised leaf longer than 2^32 entries");
+        UnionJob& job = *jobs[j];
+        job.d_docs = ws.d_union_dense_docs.as<uint32_t>() + djobs[j].out_off;
+        job.d_vals = ws.d_union_dense_vals.as<float>() + djobs[j].out_off;
+        job.len = res[j].len;
+        job.max_value = 0.0f;
+        if (res[j].max_key) {
+            const uint32_t bits = unorder_f32(res[j].max_key);
+            std::memcpy(&job.max_value, &bits, 4);
+        }
+    }
+    for (auto& [slot, gi] : write_slots) {
+        uint64_t entries = 0;
+        for (size_t k = 0; k < groups[gi].n_jobs; ++k) entries += res[groups[gi].job_begin + k].len + 8;
+        ws.timed[slot].layout_bytes += entries * 8;
+        ws.timed[slot].algorithmic_bytes += entries * 8;
+    }
+}
+}  // namespace
+
 void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st) {
     std::vector<UnionTaskH> l1, l2;
+    std::vector<UnionJob*> dense;
     for (auto& kv : table) {
         UnionJob& job = kv.second;
+        if (job.terms.size() > union_dense_min()) {  // (the lists that are non-empty in the unsharded index: every shard takes the same route)
+            dense.push_back(&job);
+            continue;
+        }
         std::vector<UList> raw;
         for (auto& t : job.terms) {
             const PostingStore& ps = *t.store;
@@ -560,7 +701,6 @@ void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStrea
             u.term_score = t.score;
             raw.push_back(u);
         }
-        if (raw.size() > 64 * 64) throw VelociError(ERR_UNSUPPORTED, "leaf expansion with more than 4096 posting lists");
         if (raw.size() <= 64) {
             UnionTaskH t;
             t.lists = std::move(raw);
@@ -578,6 +718,7 @@ void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStrea
             l2.push_back(std::move(top));
         }
     }
+    run_union_dense(idx, ws, dense, st);
     run_union_level(idx.profile.enabled, ws, l1, ws.d_union_docs[0], ws.d_union_vals[0], ws.d_union_max, ws.d_union_meta, st);
     for (auto& t : l1) {
         const uint32_t* d = ws.d_union_docs[0].as<uint32_t>() + t.out_off;

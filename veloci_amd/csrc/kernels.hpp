@@ -84,6 +84,31 @@ void launch_facet_select(hipStream_t st, uint32_t n_jobs, const FacetJob* jobs, 
 void launch_range_hits(hipStream_t st, uint32_t n_blocks, uint32_t n_jobs, const UList* ulists, const RangeJobD* jobs, const uint32_t* anchors, unsigned long long* counts);
 void launch_union(hipStream_t st, bool write, uint32_t total_spans, const UList* ulists, const UTask* tasks, const uint32_t* span_task, uint32_t* span_cnt,
                   const uint64_t* span_off, uint32_t* out_docs, float* out_vals, uint32_t* task_min);
+// ---- dense union (union_dense.hip): leaves with more lists than two levels of k_union take
+constexpr uint32_t kDenseBlockDocs = 2048;  // slab words per workgroup of the count / write passes; a job's slab is padded to whole blocks
+struct UDenseList {  // one non-empty posting list of a group of jobs; lists[n] closes the table (first == the group's postings)
+    const uint32_t* docs;
+    const uint16_t* scores;
+    uint64_t first;  // index of the list's first posting in the group's flattened order
+    float term_score;
+    uint32_t job;    // of the group
+};
+struct UDenseJob {
+    uint64_t slab_off;             // first word of the job's slab
+    uint64_t out_off;              // first entry of the job's list in the output arrays
+    uint32_t block_begin, n_blocks;  // count / write workgroups: the group's first block of this job, blocks of the job (>= 1)
+    uint32_t result, pad;          // index into the batch's UDenseResult table
+};
+struct UDenseResult {
+    uint32_t len, max_key;  // entries written; largest order_f32(value), 0 = the list is empty
+};
+void launch_union_dense_scatter(hipStream_t st, const UDenseList* lists, uint32_t n_lists, uint64_t total_postings, const UDenseJob* jobs, uint32_t* slab, uint32_t lo_doc,
+                                uint32_t range);
+// count pass + prefix sums: block_cnt[b] becomes the entries of the job before block b (block_max: n_blocks words of scratch), results[] are set
+void launch_union_dense_count(hipStream_t st, const UDenseJob* jobs, uint32_t n_jobs, uint32_t n_blocks, const uint32_t* slab, uint32_t* block_cnt, uint32_t* block_max,
+                              UDenseResult* results);
+void launch_union_dense_write(hipStream_t st, const UDenseJob* jobs, uint32_t n_jobs, uint32_t n_blocks, const uint32_t* slab, const uint32_t* block_off, uint32_t lo_doc,
+                              uint32_t* out_docs, float* out_vals);
 void launch_scan_union(hipStream_t st, bool with_or, uint32_t total_spans, const uint8_t* blobs, const uint32_t* blob_off, const uint32_t* span_base, const uint32_t* qmap,
                        uint32_t nq, uint32_t cand_cap, unsigned long long* span_keys, unsigned long long* num_hits);
 // all n_probes scan the SAME dictionary image (off / chars); matches are appended to out[0 .. out_cap) (the count keeps running beyond the cap)

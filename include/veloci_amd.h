@@ -167,6 +167,11 @@ size_t vq_debug_sort_unique_u32(uint32_t* ids, size_t n);
  * locality jobs, -2 count pre-pass, -3 range jobs), otherwise the error code the search would return.  Diagnostic: the CPU sanitizer build (`make asan`) runs it over the
  * request fixtures; tools/compile_bench.py times it. */
 int vq_debug_compile(const vq_index*, const vq_request*);
+/* The route of a regex part (a RequestSearchPart as JSON with is_regex): 0 and the sizes of its DFA when the dictionary is scanned on the
+ * device (k_dict_regex); VQ_ERR_UNSUPPORTED with the reason in vq_last_error() when the part stays on the host route (structure outside the
+ * DFA compiler, a table beyond the kernel's LDS budget, VQ_NO_REGEX_DEVICE=1); the search's own error for a part that cannot run at all.
+ * `states` / `classes` may be null. */
+int vq_debug_regex_compile(const vq_index*, const char* part_json, size_t len, uint32_t* states, uint32_t* classes);
 
 /* ---------------------------------------------------------------- results
  *

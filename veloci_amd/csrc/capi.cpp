@@ -500,6 +500,23 @@ int vq_debug_compile(const vq_index* index, const vq_request* request) {
     });
     return rc != 0 ? rc : status;
 }
+// The route a regex part (a RequestSearchPart as JSON, is_regex true) takes on `index`: 0 and the sizes of its DFA when k_dict_regex answers it,
+// VQ_ERR_UNSUPPORTED with the reason in vq_last_error when it stays on the host route, or the error a search with the part would return.
+int vq_debug_regex_compile(const vq_index* index, const char* part_json, size_t len, uint32_t* states, uint32_t* classes) {
+    return guard([&] {
+        if (!index || !part_json) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_debug_regex_compile: null argument");
+        vqreq::RequestSearchPart part;
+        try {
+            part = vqreq::search_part_from_json(vqjson::parse(part_json, len));
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        const vqregex::Compiled c = vq::regex_route(*index->idx, part);
+        if (!c.device) throw VelociError(VQ_ERR_UNSUPPORTED, "regex leaf on the host route: " + c.reason);
+        if (states) *states = c.dfa.n_states;
+        if (classes) *classes = c.dfa.n_classes;
+    });
+}
 void vq_request_free(vq_request* r) { delete r; }
 // The continuation of `request` behind the ranked hit (score, id): what a caller of the sharded partial / merge path sends for the next page of a
 // request whose top + skip reaches beyond one scan's ranking (vq_result_is_page).

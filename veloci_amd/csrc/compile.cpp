@@ -240,6 +240,23 @@ struct CountReq {
     int root_op;
 };
 
+// The two std::wregex objects of a regex leaf (the yardstick of both routes: their flags, the wrapper, their errors)
+static std::wstring regex_widen(const std::string& u8) {
+    std::wstring w;
+    for (uint32_t cp : vqtext::decode_utf8(u8)) w.push_back(wchar_t(cp));
+    return w;
+}
+static void regex_objects(const RequestSearchPart& p, std::wregex& whole, std::wregex& anywhere) {
+    try {
+        const auto flags = std::regex::ECMAScript | (p.ignore_case.value_or(true) ? std::regex::icase : std::regex::ECMAScript);
+        const std::wstring pat = regex_widen(p.terms[0]);
+        whole = std::wregex(L"[\\s\\S]*?(?:" + pat + L")", flags);
+        anywhere = std::wregex(pat, flags);
+    } catch (const std::regex_error& e) {
+        throw VelociError(ERR_INVALID_REQUEST, std::string("InvalidRequest: \"regex ") + e.what() + "\" ");
+    }
+}
+
 struct Compiler {
     const Index& idx;
     const Request& req;
@@ -349,23 +366,11 @@ struct Compiler {
     // `(?s:.)*?`), and the term is accepted when the walk ENDS in a match state; `starts_with` accepts once any prefix did.  Restated over code
     // points with std::wregex (ECMAScript grammar: the common subset of the two syntaxes; case-insensitivity beyond ASCII follows the C locale).
     std::vector<uint32_t> regex_candidates(const Dictionary& dict, const RequestSearchPart& p) {
-        auto widen = [](const std::string& u8) {
-            std::wstring w;
-            for (uint32_t cp : vqtext::decode_utf8(u8)) w.push_back(wchar_t(cp));
-            return w;
-        };
         std::wregex whole, anywhere;
-        try {
-            const auto flags = std::regex::ECMAScript | (p.ignore_case.value_or(true) ? std::regex::icase : std::regex::ECMAScript);
-            const std::wstring pat = widen(p.terms[0]);
-            whole = std::wregex(L"[\\s\\S]*?(?:" + pat + L")", flags);
-            anywhere = std::wregex(pat, flags);
-        } catch (const std::regex_error& e) {
-            throw VelociError(ERR_INVALID_REQUEST, std::string("InvalidRequest: \"regex ") + e.what() + "\" ");
-        }
+        regex_objects(p, whole, anywhere);
         std::vector<uint32_t> out;
         for (uint32_t id = 0; id < dict.terms.size(); ++id) {
-            const std::wstring w = widen(dict.terms[id]);
+            const std::wstring w = regex_widen(dict.terms[id]);
             if (p.starts_with ? std::regex_search(w, anywhere) : std::regex_match(w, whole)) out.push_back(id);
         }
         return out;
@@ -397,8 +402,15 @@ struct Compiler {
         const FuzzyProbe* probe = nullptr;
         const bool regex = p.is_regex;
         const bool scan = !regex && (lev != 0 || p.starts_with);
-        if (regex) cand = regex_candidates(dict, p);
-        else if (scan) {  // match set computed on the device before compilation (k_dict_scan), ascending == FST stream order
+        if (regex) {  // match set from k_dict_regex when the batch's probes hold the leaf, else the host walk; scored on the host either way
+            const FuzzyProbe* fp = nullptr;
+            if (fuzzy) {
+                auto it = fuzzy->find(fuzzy_key(p));
+                if (it != fuzzy->end() && it->second.regex && it->second.answered && it->second.status == 0) fp = &it->second;
+            }
+            if (fp) cand = fp->matches;
+            else cand = regex_candidates(dict, p);
+        } else if (scan) {  // match set computed on the device before compilation (k_dict_scan), ascending == FST stream order
             const FuzzyProbe* fp = nullptr;
             if (fuzzy) {
                 auto it = fuzzy->find(fuzzy_key(p));
@@ -2731,11 +2743,60 @@ std::string fuzzy_key(const RequestSearchPart& p) {
     key_s(k, path);
     key_s(k, p.terms.empty() ? std::string() : p.terms[0]);
     k += std::to_string(clamped_lev(p)) + (p.starts_with ? "p" : "-") + (p.ignore_case ? (*p.ignore_case ? "T" : "F") : "N");
+    if (p.is_regex) k += 'R';
     return k;
 }
 bool needs_dictionary_scan(const RequestSearchPart& p) { return !p.terms.empty() && !p.is_regex && (clamped_lev(p) != 0 || p.starts_with); }
 
+// VQ_NO_REGEX_DEVICE=1: every regex leaf stays on the host route
+static bool regex_device_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("VQ_NO_REGEX_DEVICE");
+        return !(e && *e && std::string(e) != "0");
+    }();
+    return on;
+}
+vqregex::Compiled regex_route(const Index& idx, const RequestSearchPart& p) {
+    if (!p.is_regex) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "not a regex part (is_regex is false)");
+    if (p.terms.empty()) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"terms is empty\" ");
+    std::string path = p.path;
+    if (!ends_with(path, TEXTINDEX)) path += TEXTINDEX;
+    auto dit = idx.dict.find(path);
+    if (dit == idx.dict.end()) throw VelociError(ERR_FST_NOT_FOUND, "field does not exist " + path + " (fst not found)");
+    {  // first, always: an invalid pattern is the host route's error, word for word
+        std::wregex whole, anywhere;
+        regex_objects(p, whole, anywhere);
+    }
+    if (!regex_device_enabled()) {
+        vqregex::Compiled c;
+        c.reason = "VQ_NO_REGEX_DEVICE is set";
+        return c;
+    }
+    const Dictionary& d = dit->second;
+    return vqregex::compile(vqtext::decode_utf8(p.terms[0]), p.ignore_case.value_or(true), p.starts_with, d.alphabet, *d.regex_atoms);
+}
+static void probe_regex_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table) {
+    if (!regex_device_enabled() || p.terms.empty()) return;
+    const std::string key = fuzzy_key(p);
+    if (table.count(key)) return;
+    vqregex::Compiled c;
+    try {
+        c = regex_route(idx, p);
+    } catch (const VelociError&) {
+        return;  // the compiler reports it, request by request
+    }
+    if (!c.device) return;  // host route (Compiler::regex_candidates)
+    FuzzyProbe fp;
+    fp.key = key;
+    fp.path = p.path;
+    if (!ends_with(fp.path, TEXTINDEX)) fp.path += TEXTINDEX;
+    fp.regex = true;
+    fp.dfa = std::move(c.dfa);
+    table.emplace(key, std::move(fp));
+}
+
 static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table) {
+    if (p.is_regex) return probe_regex_part(idx, p, table);
     if (!needs_dictionary_scan(p)) return;
     const std::string key = fuzzy_key(p);
     if (table.count(key)) return;

@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "request.hpp"
 #include "hostpool.hpp"
+#include "regex_dfa.hpp"
 
 namespace vq {
 
@@ -165,6 +166,11 @@ struct Dictionary {  // term dictionary of one text field
     DevBuf d_off;             // u32 [T + 1]
     DevBuf d_raw;             // u16 or u32 (char_bytes)
     DevBuf d_low;             // u16 or u32 (char_bytes)
+    // regex leaves (k_dict_regex): the distinct code points of the terms, ascending; the device holds the part from U+0080 on
+    std::vector<uint32_t> alphabet;
+    uint32_t alphabet_ascii = 0;  // entries of `alphabet` below 128
+    DevBuf d_alpha;               // u32 [alphabet.size() - alphabet_ascii]
+    std::unique_ptr<vqregex::AtomCache> regex_atoms;  // (atom text, icase) -> members of the alphabet, filled by the leaves that ask
 };
 
 struct Index;
@@ -182,10 +188,16 @@ struct FuzzyProbe {  // one dictionary scan of a batch (get_text_lines_from_fst,
     bool check_prefix = false;
     int status = 0;
     std::string error;
+    bool regex = false;               // a regex leaf whose pattern compiled (k_dict_regex): `dfa` is the probe, `matches` the result, scores stay with the host
+    vqregex::Dfa dfa;
+    bool answered = false;            // run_fuzzy_probes has filled `matches`
 };
 using FuzzyTable = std::map<std::string, FuzzyProbe>;
 std::string fuzzy_key(const vqreq::RequestSearchPart& p);
 bool needs_dictionary_scan(const vqreq::RequestSearchPart& p);
+// The route of a regex part: its DFA when k_dict_regex takes it, else the reason it stays on the host.  Throws what the search would answer for
+// a part that cannot run at all (no terms, unknown field, invalid pattern).
+vqregex::Compiled regex_route(const Index& idx, const vqreq::RequestSearchPart& p);
 void collect_fuzzy_probes(const Index& idx, const vqreq::Request& req, FuzzyTable& table);
 struct Workspace;
 void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStream_t st);
@@ -418,7 +430,7 @@ constexpr int kWorkspaces = 4;  // batches in flight per index (host compile of 
 
 // Kernels the profiler accounts separately (vq_profile_json): the pre-passes, one entry per scan class, the merges.
 enum KernelId : int {
-    K_DICT_SCAN = 0, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_RING, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
+    K_DICT_SCAN = 0, K_DICT_REGEX, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_RING, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
     K_SCAN_WIDE, K_TILE_SCAN, K_MERGE_SPANS, K_FINALIZE, K_FACET_SELECT, K_LOCALITY, K_BOOST1N, K_COUNT_
 };
 extern const char* const kKernelNames[K_COUNT_];
@@ -446,6 +458,7 @@ struct Workspace {  // scratch of one in-flight batch
     DevBuf d_loc_a, d_loc_b, d_loc_pairs_a, d_loc_pairs_b, d_loc_meta, d_loc_tmp, d_loc_docs, d_loc_vals;  // text locality pre-pass (K7)
     DevBuf d_b1n_a, d_b1n_b, d_b1n_meta, d_b1n_tmp, d_b1n_docs, d_b1n_vals;                              // 1:n boost lists (K10)
     DevBuf d_probe_desc, d_probe_counts, d_probe_ids;                    // dictionary scans (k_dict_scan): kept, so that no hipFree synchronises the device mid-pipeline
+    DevBuf d_regex_tabs;                                                 // regex probes (k_dict_regex): descriptors + table pool
 };
 
 struct KernelProfile {

@@ -39,7 +39,7 @@ static bool timing_enabled() {
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
+const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
                                             "k_scan_simple<2,rich>", "k_scan_ring (AND)", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
                                             "k_merge_spans", "k_finalize", "k_facet_select", "k_locality", "k_boost1n"};
 
@@ -216,9 +216,13 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
     for (auto& kv : table)
         if (kv.second.status == 0) todo.push_back(&kv.second);
     if (todo.empty()) return;
-    auto image_of = [&](const FuzzyProbe& fp) -> const void* {  // the dictionary image a probe scans
+    auto image_of = [&](const FuzzyProbe& fp) -> const void* {  // the dictionary image a probe scans (a regex probe: always the raw one)
         const Dictionary& d = idx.dict.at(fp.path);
-        return fp.ci ? d.d_low.p : d.d_raw.p;
+        return fp.ci && !fp.regex ? d.d_low.p : d.d_raw.p;
+    };
+    auto small_tables = [&](const FuzzyProbe& fp) {  // a regex probe whose tables fit the small form of k_dict_regex
+        const Dictionary& d = idx.dict.at(fp.path);
+        return vqregex::lds_table_bytes(fp.dfa.n_states, fp.dfa.n_classes, d.alphabet.size() - d.alphabet_ascii) <= vqregex::kLdsTableBytesSmall;
     };
     // k_dict_scan takes a 16-bit image and a query of <= 64 code points below U+10000 inline; every other probe goes to k_dict_scan_wide, with
     // its code points as u32 in a side pool
@@ -228,19 +232,24 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
         return wide;
     };
     // probes of one image (and form) next to each other: a launch scans ONE image for a run of probes (blocks answer 16 probes per pass over their terms)
+    // the regex probes behind the others, those of one dictionary and one table size next to each other: todo[n_scan ..) go to k_dict_regex
     std::stable_sort(todo.begin(), todo.end(), [&](const FuzzyProbe* a, const FuzzyProbe* b) {
+        if (a->regex != b->regex) return b->regex;
         const void *ia = image_of(*a), *ib = image_of(*b);
+        if (a->regex) return ia != ib ? ia < ib : small_tables(*a) > small_tables(*b);
         return ia != ib ? ia < ib : pooled(*a) < pooled(*b);
     });
-    std::vector<DictProbe> probes(todo.size());
+    size_t n_scan = 0;
+    while (n_scan < todo.size() && !todo[n_scan]->regex) ++n_scan;
+    std::vector<DictProbe> probes(n_scan);
     std::vector<DictProbeW> wprobes;  // indexed like `probes` (only the pooled ones are filled in); empty when no probe is pooled
     std::vector<uint32_t> pool;
     std::vector<uint8_t> host_scored(todo.size(), 0), is_pooled(todo.size(), 0);
-    for (size_t i = 0; i < todo.size(); ++i) {
+    for (size_t i = 0; i < n_scan; ++i) {
         const FuzzyProbe& fp = *todo[i];
         const auto lcps = vqtext::decode_utf8(fp.lower_term);  // scoring side: the lower-cased term as a whole (search_field.rs:298-300)
         if (pooled(fp)) {
-            if (wprobes.empty()) wprobes.resize(todo.size());
+            if (wprobes.empty()) wprobes.resize(n_scan);
             is_pooled[i] = 1;
             DictProbeW& W = wprobes[i];
             std::memset(&W, 0, sizeof W);
@@ -287,7 +296,31 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
     const size_t w_at = align_up(probes.size() * sizeof(DictProbe), 256), pool_at = w_at + align_up(wprobes.size() * sizeof(DictProbeW), 256);
     d_probes.ensure(pool_at + pool.size() * 4 + 16);
     d_count.ensure(64);
-    VQ_HIP(hipMemcpyAsync(d_probes.p, probes.data(), probes.size() * sizeof(DictProbe), hipMemcpyHostToDevice, st));
+    // regex probes: [RegexProbeD x n][pool: every probe's tables in the kernel's format]
+    std::vector<RegexProbeD> rprobes;
+    std::vector<uint16_t> rpool;
+    for (size_t i = n_scan; i < todo.size(); ++i) {
+        const FuzzyProbe& fp = *todo[i];
+        const Dictionary& d = idx.dict.at(fp.path);
+        const vqregex::Dfa& A = fp.dfa;
+        const uint32_t C = A.n_classes, n_next = A.n_states * C, n_alpha = uint32_t(d.alphabet.size()) - d.alphabet_ascii;
+        RegexProbeD R{uint32_t(rpool.size()), n_next, A.start * C, A.first_accept * C};
+        rprobes.push_back(R);
+        const size_t end = rpool.size() + regex_words16(n_next, n_alpha);
+        for (uint16_t to : A.next) rpool.push_back(uint16_t(to * C));
+        uint16_t ascii[128] = {};
+        for (uint32_t k = 0; k < d.alphabet_ascii; ++k) ascii[d.alphabet[k]] = A.cls[k];
+        rpool.insert(rpool.end(), ascii, ascii + 128);
+        rpool.insert(rpool.end(), A.cls.begin() + d.alphabet_ascii, A.cls.end());
+        rpool.resize(end, uint16_t(0));
+    }
+    const size_t rpool_at = align_up(rprobes.size() * sizeof(RegexProbeD), 256);
+    if (!rprobes.empty()) {
+        ws.d_regex_tabs.ensure(rpool_at + rpool.size() * 2 + 16);
+        VQ_HIP(hipMemcpyAsync(ws.d_regex_tabs.p, rprobes.data(), rprobes.size() * sizeof(RegexProbeD), hipMemcpyHostToDevice, st));
+        VQ_HIP(hipMemcpyAsync(ws.d_regex_tabs.as<uint8_t>() + rpool_at, rpool.data(), rpool.size() * 2, hipMemcpyHostToDevice, st));
+    }
+    if (n_scan) VQ_HIP(hipMemcpyAsync(d_probes.p, probes.data(), probes.size() * sizeof(DictProbe), hipMemcpyHostToDevice, st));
     if (!wprobes.empty()) {
         VQ_HIP(hipMemcpyAsync(d_probes.as<uint8_t>() + w_at, wprobes.data(), wprobes.size() * sizeof(DictProbeW), hipMemcpyHostToDevice, st));
         if (!pool.empty()) VQ_HIP(hipMemcpyAsync(d_probes.as<uint8_t>() + pool_at, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, st));
@@ -297,16 +330,16 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
     for (int pass = 0; pass < 2; ++pass) {  // pass 1 only when the matches outgrew the first guess (the count is exact then)
         d_out.ensure(size_t(cap) * sizeof(DictMatch) + 16);
         VQ_HIP(hipMemsetAsync(d_count.p, 0, 4, st));
-        {
+        if (n_scan) {
             uint64_t dict_bytes = 0, layout = 0;  // every probe reads its dictionary once (offsets + code points) ...
-            for (FuzzyProbe* fp : todo) {
-                const Dictionary& d = idx.dict.at(fp->path);
+            for (size_t i = 0; i < n_scan; ++i) {
+                const Dictionary& d = idx.dict.at(todo[i]->path);
                 dict_bytes += d.d_off.bytes + d.d_low.bytes;
             }
-            LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_SCAN, 0, dict_bytes, todo.size());
-            for (size_t g0 = 0; g0 < todo.size();) {  // one launch per run of probes over the same image
+            LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_SCAN, 0, dict_bytes, n_scan);
+            for (size_t g0 = 0; g0 < n_scan;) {  // one launch per run of probes over the same image
                 size_t g1 = g0 + 1;
-                while (g1 < todo.size() && image_of(*todo[g1]) == image_of(*todo[g0]) && is_pooled[g1] == is_pooled[g0]) ++g1;
+                while (g1 < n_scan && image_of(*todo[g1]) == image_of(*todo[g0]) && is_pooled[g1] == is_pooled[g0]) ++g1;
                 const Dictionary& d = idx.dict.at(todo[g0]->path);
                 if (is_pooled[g0])
                     launch_dict_scan_wide(st, d.char_bytes, reinterpret_cast<const DictProbeW*>(d_probes.as<uint8_t>() + w_at) + g0,
@@ -320,6 +353,25 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
                 g0 = g1;
             }
             if (!ws.timed.empty() && idx.profile.enabled) ws.timed.back().layout_bytes = layout;
+        }
+        if (n_scan < todo.size()) {  // k_dict_regex: grid.y = probe, every probe reads its dictionary's offsets and raw image (and its own tables)
+            uint64_t dict_bytes = 0;
+            for (size_t i = n_scan; i < todo.size(); ++i) {
+                const Dictionary& d = idx.dict.at(todo[i]->path);
+                dict_bytes += d.d_off.bytes + d.d_raw.bytes;
+            }
+            LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_REGEX, dict_bytes + rpool.size() * 2, dict_bytes, todo.size() - n_scan);
+            for (size_t g0 = n_scan; g0 < todo.size();) {  // one launch per run of probes over one dictionary with tables of one size class
+                size_t g1 = g0 + 1;
+                const bool small = small_tables(*todo[g0]);
+                while (g1 < todo.size() && image_of(*todo[g1]) == image_of(*todo[g0]) && small_tables(*todo[g1]) == small) ++g1;
+                const Dictionary& d = idx.dict.at(todo[g0]->path);
+                launch_dict_regex(st, d.char_bytes, small, ws.d_regex_tabs.as<RegexProbeD>() + (g0 - n_scan),
+                                  reinterpret_cast<const uint16_t*>(ws.d_regex_tabs.as<uint8_t>() + rpool_at), d.d_alpha.as<uint32_t>(),
+                                  uint32_t(d.alphabet.size()) - d.alphabet_ascii, uint32_t(g0), uint32_t(g1 - g0), d.d_off.as<uint32_t>(), d.d_raw.p,
+                                  uint32_t(d.terms.size()), d_count.as<uint32_t>(), cap, d_out.as<DictMatch>());
+                g0 = g1;
+            }
         }
         VQ_HIP(hipGetLastError());
         uint32_t count = 0;
@@ -356,6 +408,11 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
         FuzzyProbe& fp = *todo[i];
         fp.matches.clear();
         fp.scores.clear();
+        fp.answered = true;
+        if (fp.regex) {  // the match set only: regex hits are scored by the compiler's host branch
+            for (; r < recs.size() && recs[r].probe == i; ++r) fp.matches.push_back(recs[r].term);
+            continue;
+        }
         const Dictionary& dict = idx.dict.at(fp.path);
         for (; r < recs.size() && recs[r].probe == i; ++r) {
             fp.matches.push_back(recs[r].term);

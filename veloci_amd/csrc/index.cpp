@@ -179,8 +179,11 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         {  // device image for k_dict_scan: code points as u16 (raw + lower-cased), CSR over the terms; as u32 when some term has one above U+FFFF
             std::vector<uint32_t> off(d.terms.size() + 1, 0u);
             std::vector<uint32_t> raw, low;
+            std::vector<uint64_t> seen(0x110000 / 64, 0ull);  // the dictionary's alphabet (regex leaves), collected on the way
             for (uint32_t i = 0; i < d.terms.size(); ++i) {
                 for (uint32_t cp : vqtext::decode_utf8(d.terms[i])) {
+                    if (cp < 0x110000u) seen[cp >> 6] |= 1ull << (cp & 63u);
+                    else d.alphabet.push_back(cp);
                     if (cp > 0xFFFFu) d.char_bytes = 4;
                     if (cp == 0x130u) d.low_exact = false;  // lower-cases to TWO code points ("i" + U+0307): the image is per code point
                     raw.push_back(cp);
@@ -203,6 +206,15 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
             image(d.d_raw, raw);
             image(d.d_low, low);
             idx->device_bytes += d.d_off.bytes + d.d_raw.bytes + d.d_low.bytes;
+            for (uint32_t w = 0; w < seen.size(); ++w)
+                for (uint64_t bits = seen[w]; bits; bits &= bits - 1) d.alphabet.push_back(w * 64u + uint32_t(__builtin_ctzll(bits)));
+            std::sort(d.alphabet.begin(), d.alphabet.end());
+            d.alphabet.erase(std::unique(d.alphabet.begin(), d.alphabet.end()), d.alphabet.end());
+            d.alphabet_ascii = uint32_t(std::lower_bound(d.alphabet.begin(), d.alphabet.end(), 128u) - d.alphabet.begin());
+            d.d_alpha.alloc((d.alphabet.size() - d.alphabet_ascii) * 4 + 16);
+            d.d_alpha.upload(d.alphabet.data() + d.alphabet_ascii, (d.alphabet.size() - d.alphabet_ascii) * 4);
+            idx->device_bytes += d.d_alpha.bytes;
+            d.regex_atoms = std::make_unique<vqregex::AtomCache>();
         }
         idx->dict.emplace(path, std::move(d));
     }

@@ -117,6 +117,19 @@ void launch_dict_scan(hipStream_t st, const DictProbe* d_probes, uint32_t probe_
 // the same over a 16-bit (char_bytes 2) or 32-bit (char_bytes 4) image, with the probes' queries in `pool`
 void launch_dict_scan_wide(hipStream_t st, uint32_t char_bytes, const DictProbeW* d_probes, const uint32_t* pool, uint32_t probe_base, uint32_t n_probes, const uint32_t* off,
                            const void* chars, const void* low_chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out);
+// ---- regex leaves (dict_regex.hip): the probe's DFA (regex_dfa.hpp) in the kernel's format.  Its tables are u16 words of a pool, at
+// [tab_off, + regex_words16): next[states * classes] with the states premultiplied by the number of classes, the class of every code point
+// below 128, the class of the k-th non-ASCII code point of the dictionary's alphabet; tab_off is a multiple of 8 (16-byte loads).
+struct RegexProbeD {
+    uint32_t tab_off, n_next;      // n_next = states * classes (< 65536)
+    uint32_t start, first_accept;  // premultiplied: the walk starts at `start`, a term matches when it ends at or above `first_accept`
+};
+__host__ __device__ inline uint32_t regex_words16(uint32_t n_next, uint32_t n_alpha) { return (n_next + 128u + n_alpha + 7u) & ~7u; }
+// n_probes probes (d_probes[0 ..), numbered from probe_base in the output) over ONE dictionary: its offsets, its RAW image, the non-ASCII part
+// of its alphabet.  small_tables: every probe's tables fit vqregex::kLdsTableBytesSmall.  Output as launch_dict_scan (info = 0).
+void launch_dict_regex(hipStream_t st, uint32_t char_bytes, bool small_tables, const RegexProbeD* d_probes, const uint16_t* pool, const uint32_t* alpha, uint32_t n_alpha,
+                       uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const void* chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap,
+                       DictMatch* out);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

@@ -199,6 +199,22 @@ class Index:
     def profile_enable(self, on=True):
         _lib.check(self.L.vq_profile_enable(self.h, int(on)))
 
+    def regex_route(self, part):
+        """vq_debug_regex_compile: the route a regex part (a RequestSearchPart as dict or JSON, is_regex true) takes on this index.
+        -> {"device": True, "states": n, "classes": c} when k_dict_regex scans the dictionary for it, {"device": False, "reason": text} when it
+        stays on the host route; raises VelociError for a part that cannot run at all (invalid pattern, unknown field)."""
+        import json
+        if isinstance(part, dict):
+            part = json.dumps(part)
+        if isinstance(part, str):
+            part = part.encode()
+        states, classes = C.c_uint32(), C.c_uint32()
+        rc = self.L.vq_debug_regex_compile(self.h, part, len(part), C.byref(states), C.byref(classes))
+        if rc == 4:  # VQ_ERR_UNSUPPORTED
+            return {"device": False, "reason": self.L.vq_last_error().decode("utf-8", "replace")}
+        _lib.check(rc)
+        return {"device": True, "states": int(states.value), "classes": int(classes.value)}
+
     def profile_json(self, reset=True):
         """vq_profile_json: per-kernel device time, launches, layout / algorithmic bytes since the last reset."""
         import json

@@ -3,17 +3,23 @@
 // exact / prefix dictionary probes are answered by a plain loop, see launch_dict_scan below).  What this build can run is everything in front of
 // the first launch: index staging (index.cpp), request parsing, query compilation (compile.cpp), the C ABI's argument handling — under
 // AddressSanitizer + UndefinedBehaviorSanitizer.  Never linked into the product library.
+// With VQ_STUB_LAUNCH_LOG=<file> every launcher appends one JSON line to that file (tests/test_launch_plan_cpu.py): its name and scalar arguments; a
+// scan launcher also the span_base / qmap tables it was handed ("device" memory is host memory here) and which of its output pointers are set.
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <mutex>
+#include <string>
 
 #include "../../veloci_amd/csrc/engine.hpp"
 
 extern "C" {
 hipError_t hipMalloc(void** p, size_t n) {
-    *p = std::malloc(n ? n : 1);
+    *p = std::calloc(n ? n : 1, 1);  // zeroed: what a launch that did nothing "wrote" reads the same in every run (the recorded launch plan depends on it)
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 hipError_t hipFree(void* p) {
@@ -108,48 +114,112 @@ static void no_device(const char* what) {
     if (noop) return;
     throw vqreq::VelociError(vqreq::ERR_DEVICE, std::string("device layer stubbed: ") + what);
 }
+static void log_launch(const char* name, std::initializer_list<long long> scalars, const uint32_t* span_base = nullptr, const uint32_t* qmap = nullptr, uint32_t nq = 0) {
+    static const char* path = std::getenv("VQ_STUB_LAUNCH_LOG");
+    if (!path) return;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    std::FILE* f = std::fopen(path, "a");
+    if (!f) return;
+    std::fprintf(f, "{\"launch\":\"%s\",\"args\":[", name);
+    const char* sep = "";
+    for (long long v : scalars) std::fprintf(f, "%s%lld", sep, v), sep = ",";
+    std::fprintf(f, "]");
+    if (span_base) {
+        std::fprintf(f, ",\"span_base\":[");
+        for (uint32_t i = 0; i <= nq; ++i) std::fprintf(f, "%s%u", i ? "," : "", span_base[i]);
+        std::fprintf(f, "],\"qmap\":[");
+        for (uint32_t i = 0; i < nq; ++i) std::fprintf(f, "%s%u", i ? "," : "", qmap[i]);
+        std::fprintf(f, "]");
+    }
+    std::fprintf(f, "}\n");
+    std::fclose(f);
+}
 size_t tile_scan_lds_bytes(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t) { return 0; }
 size_t scan_simple_lds_bytes(uint32_t, uint32_t, uint32_t, bool) { return 0; }
 size_t scan_wide_lds_bytes(uint32_t, uint32_t, uint32_t) { return 0; }
+size_t scan_probe_lds_bytes(uint32_t, uint32_t, uint32_t, uint32_t) { return 0; }
+uint32_t debug_probe_occupancy(uint32_t, size_t) { return 0; }
 int debug_facet_select(const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*) { return -1; }
 uint32_t debug_div100_mismatches() {
     no_device("debug_div100_mismatches");
     return 0;
 }
-void launch_tile_scan(hipStream_t, uint32_t, size_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, unsigned long long*,
-                      unsigned long long*, uint32_t*, bool, uint32_t, bool) { no_device("k_tile_scan"); }
-void launch_scan_leaf_f32(hipStream_t, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, unsigned long long*, unsigned long long*, uint32_t*) {
+// ---- the scan launchers
+void launch_tile_scan(hipStream_t, uint32_t total_spans, size_t lds_bytes, const uint8_t*, const uint32_t*, const uint32_t* span_base, const uint32_t* qmap, uint32_t nq,
+                      uint32_t stack_depth, uint32_t cand_cap, uint32_t desc_cap, unsigned long long*, unsigned long long*, uint32_t* hist, bool queue, uint32_t ml, bool facet_cache) {
+    log_launch("k_tile_scan", {total_spans, (long long)lds_bytes, nq, stack_depth, cand_cap, desc_cap, hist != nullptr, queue, ml, facet_cache}, span_base, qmap, nq);
+    no_device("k_tile_scan");
+}
+void launch_scan_leaf_f32(hipStream_t, uint32_t total_spans, const uint8_t*, const uint32_t*, const uint32_t* span_base, const uint32_t* qmap, uint32_t nq, uint32_t cand_cap,
+                          unsigned long long*, unsigned long long*, uint32_t* hist) {
+    log_launch("k_scan_leaf_f32", {total_spans, nq, cand_cap, hist != nullptr}, span_base, qmap, nq);
     no_device("k_scan_leaf_f32");
 }
-void launch_scan_simple(hipStream_t, bool, uint32_t, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, unsigned long long*, unsigned long long*,
-                        uint32_t*, bool) { no_device("k_scan_simple"); }
-void launch_scan_wide(hipStream_t, uint32_t, uint32_t, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, unsigned long long*,
-                      unsigned long long*) { no_device("k_scan_wide"); }
-void launch_scan_probe(hipStream_t, uint32_t, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, unsigned long long*, unsigned long long*, bool, bool) {
+void launch_scan_simple(hipStream_t, bool wide, uint32_t n_scatter, uint32_t total_spans, const uint8_t*, const uint32_t*, const uint32_t* span_base, const uint32_t* qmap, uint32_t nq,
+                        uint32_t cand_cap, unsigned long long*, unsigned long long*, uint32_t* hist, bool facet_cache) {
+    log_launch("k_scan_simple", {wide, n_scatter, total_spans, nq, cand_cap, hist != nullptr, facet_cache}, span_base, qmap, nq);
+    no_device("k_scan_simple");
+}
+void launch_scan_wide(hipStream_t, uint32_t max_leaves, uint32_t max_scatter, uint32_t total_spans, const uint8_t*, const uint32_t*, const uint32_t* span_base, const uint32_t* qmap,
+                      uint32_t nq, uint32_t cand_cap, unsigned long long*, unsigned long long*) {
+    log_launch("k_scan_wide", {max_leaves, max_scatter, total_spans, nq, cand_cap}, span_base, qmap, nq);
+    no_device("k_scan_wide");
+}
+void launch_scan_probe_shape(hipStream_t, uint32_t shape, uint32_t na_seen, uint32_t arr_slot, uint32_t total_spans, const uint8_t*, const uint32_t*, const uint32_t* span_base,
+                             const uint32_t* qmap, uint32_t nq, uint32_t cand_cap, unsigned long long*, unsigned long long*) {
+    log_launch("k_scan_probe", {shape, na_seen, arr_slot, total_spans, nq, cand_cap}, span_base, qmap, nq);
     no_device("k_scan_probe");
 }
-size_t scan_probe_lds_bytes(uint32_t, uint32_t) { return 0; }
-void launch_scan_ring(hipStream_t, uint32_t, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t*, unsigned long long*,
-                      unsigned long long*) {
-    no_device("k_scan_ring");
+void launch_scan_union(hipStream_t, bool with_or, uint32_t total_spans, const uint8_t*, const uint32_t*, const uint32_t* span_base, const uint32_t* qmap, uint32_t nq, uint32_t cand_cap,
+                       unsigned long long*, unsigned long long*) {
+    log_launch("k_scan_union", {with_or, total_spans, nq, cand_cap}, span_base, qmap, nq);
+    no_device("k_scan_union");
 }
-uint32_t scan_ring_consumers(uint32_t) { return 10; }
-uint32_t scan_ring_slots(uint32_t, uint32_t) { return 3; }
-size_t scan_ring_lds_bytes(uint32_t, uint32_t, uint32_t) { return 0; }
-void launch_merge_spans(hipStream_t, uint32_t, const uint8_t*, const uint32_t*, const unsigned long long*, unsigned long long*) { no_device("k_merge_spans"); }
-void launch_finalize(hipStream_t, uint32_t, const uint8_t*, const uint32_t*, const uint8_t*, uint32_t, size_t, const PartialLayout&, uint32_t*, float*, uint32_t*, unsigned long long*) {
+// ---- merge and pre-pass launchers
+void launch_merge_spans(hipStream_t, uint32_t nq, const uint8_t*, const uint32_t*, const unsigned long long*, unsigned long long*) {
+    log_launch("k_merge_spans", {nq});
+    no_device("k_merge_spans");
+}
+void launch_finalize(hipStream_t, uint32_t nq, const uint8_t*, const uint32_t*, const uint8_t*, uint32_t num_shards, size_t, const PartialLayout&, uint32_t*, float*, uint32_t*,
+                     unsigned long long*) {
+    log_launch("k_finalize", {nq, num_shards});
     no_device("k_finalize");
 }
-void launch_facet_select(hipStream_t, uint32_t, const FacetJob*, const uint32_t*, uint32_t*, uint32_t*, uint32_t*) { no_device("k_facet_select"); }
-void launch_range_hits(hipStream_t, uint32_t, uint32_t, const UList*, const RangeJobD*, const uint32_t*, unsigned long long*) { no_device("k_range_hits"); }
-void launch_union(hipStream_t, bool, uint32_t, const UList*, const UTask*, const uint32_t*, uint32_t*, const uint64_t*, uint32_t*, float*, uint32_t*) { no_device("k_union"); }
-void launch_scan_union(hipStream_t, bool, uint32_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, unsigned long long*, unsigned long long*) {
-    no_device("k_scan_union");
+void launch_facet_select(hipStream_t, uint32_t n_jobs, const FacetJob*, const uint32_t*, uint32_t*, uint32_t*, uint32_t*) {
+    log_launch("k_facet_select", {n_jobs});
+    no_device("k_facet_select");
+}
+void launch_range_hits(hipStream_t, uint32_t n_blocks, uint32_t n_jobs, const UList*, const RangeJobD*, const uint32_t*, unsigned long long*) {
+    log_launch("k_range_hits", {n_blocks, n_jobs});
+    no_device("k_range_hits");
+}
+void launch_union(hipStream_t, bool write, uint32_t total_spans, const UList*, const UTask*, const uint32_t*, uint32_t*, const uint64_t*, uint32_t*, float*, uint32_t*) {
+    log_launch("k_union", {write, total_spans});
+    no_device("k_union");
+}
+void launch_union_dense_scatter(hipStream_t, const UDenseList*, uint32_t n_lists, uint64_t total_postings, const UDenseJob*, uint32_t*, uint32_t lo_doc, uint32_t range) {
+    log_launch("k_union_dense_scatter", {n_lists, (long long)total_postings, lo_doc, range});
+    no_device("k_union_dense_scatter");
+}
+void launch_union_dense_count(hipStream_t, const UDenseJob*, uint32_t n_jobs, uint32_t n_blocks, const uint32_t*, uint32_t*, uint32_t*, UDenseResult*) {
+    log_launch("k_union_dense_count", {n_jobs, n_blocks});
+    no_device("k_union_dense_count");
+}
+void launch_union_dense_write(hipStream_t, const UDenseJob*, uint32_t n_jobs, uint32_t n_blocks, const uint32_t*, const uint32_t*, uint32_t lo_doc, uint32_t*, float*) {
+    log_launch("k_union_dense_write", {n_jobs, n_blocks, lo_doc});
+    no_device("k_union_dense_write");
+}
+void launch_dict_scan_wide(hipStream_t, uint32_t char_bytes, const DictProbeW*, const uint32_t*, uint32_t probe_base, uint32_t n_probes, const uint32_t*, const void*, const void*,
+                           uint32_t num_terms, uint32_t*, uint32_t out_cap, DictMatch*) {
+    log_launch("k_dict_scan_wide", {char_bytes, probe_base, n_probes, num_terms, out_cap});
+    no_device("k_dict_scan_wide");
 }
 // VQ_STUB_DICT_SCAN=1 (tools/host_profile.py only): exact / prefix probes answered by a plain loop, so that the host compiler can be timed on this
 // machine on requests with prefix leaves.  The sanitizer test leaves it off: there every launcher throws.
 void launch_dict_scan(hipStream_t, const DictProbe* probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const uint16_t* chars, const uint16_t* low_chars,
                       uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out) {
+    log_launch("k_dict_scan", {probe_base, n_probes, num_terms, out_cap});
     if (!std::getenv("VQ_STUB_DICT_SCAN")) no_device("k_dict_scan");
     for (uint32_t p = 0; p < n_probes; ++p) {
         const DictProbe& P = probes[p];
@@ -172,19 +242,80 @@ void launch_dict_scan(hipStream_t, const DictProbe* probes, uint32_t probe_base,
         }
     }
 }
-void launch_loc_gather(hipStream_t, const LocRow*, uint32_t, const uint32_t*, uint32_t*) { no_device("k_loc_gather"); }
-void launch_loc_expand(hipStream_t, bool, const LocJob*, uint32_t, const uint32_t*, uint32_t, uint32_t*, unsigned long long*) { no_device("k_loc_expand"); }
-void launch_loc_compact(hipStream_t, const LocJob*, uint32_t, const unsigned long long*, uint32_t*, float*, uint32_t*) { no_device("k_loc_compact"); }
-size_t seg_sort_u32(void*, size_t, const uint32_t*, uint32_t*, uint32_t, uint32_t, const uint32_t*, const uint32_t*, hipStream_t) {
+void launch_loc_gather(hipStream_t, const LocRow*, uint32_t n_rows, const uint32_t*, uint32_t*) {
+    log_launch("k_loc_gather", {n_rows});
+    no_device("k_loc_gather");
+}
+void launch_loc_expand(hipStream_t, bool write, const LocJob*, uint32_t n_jobs, const uint32_t*, uint32_t n, uint32_t*, unsigned long long*) {
+    log_launch("k_loc_expand", {write, n_jobs, n});
+    no_device("k_loc_expand");
+}
+void launch_loc_compact(hipStream_t, const LocJob*, uint32_t n_jobs, const unsigned long long*, uint32_t*, float*, uint32_t*) {
+    log_launch("k_loc_compact", {n_jobs});
+    no_device("k_loc_compact");
+}
+size_t seg_sort_u32(void*, size_t, const uint32_t*, uint32_t*, uint32_t n, uint32_t nseg, const uint32_t*, const uint32_t*, hipStream_t) {
+    log_launch("seg_sort_u32", {n, nseg});
     no_device("seg_sort_u32");
     return 0;
 }
-size_t seg_sort_u64(void*, size_t, const unsigned long long*, unsigned long long*, uint32_t, uint32_t, const uint32_t*, const uint32_t*, hipStream_t) {
+size_t seg_sort_u64(void*, size_t, const unsigned long long*, unsigned long long*, uint32_t n, uint32_t nseg, const uint32_t*, const uint32_t*, hipStream_t) {
+    log_launch("seg_sort_u64", {n, nseg});
     no_device("seg_sort_u64");
     return 0;
 }
-void launch_b1n_map(hipStream_t, const B1nJob*, uint32_t, const uint32_t*, uint32_t*, float*, B1nResult*) { no_device("k_b1n_map"); }
-void launch_explain(hipStream_t, uint32_t, const ExQuery*, const uint32_t*, const uint32_t*, const ExOp*, const uint16_t*, const ExList*, const DColBoost*, uint32_t*) { no_device("k_explain"); }
+void launch_b1n_map(hipStream_t, const B1nJob*, uint32_t n_jobs, const uint32_t*, uint32_t*, float*, B1nResult*) {
+    log_launch("k_b1n_map", {n_jobs});
+    no_device("k_b1n_map");
+}
+void launch_explain(hipStream_t, uint32_t n_docs, const ExQuery*, const uint32_t*, const uint32_t*, const ExOp*, const uint16_t*, const ExList*, const DColBoost*, uint32_t*) {
+    log_launch("k_explain", {n_docs});
+    no_device("k_explain");
+}
+// With VQ_STUB_DICT_SCAN=1 the regex scan is answered on the host as well, walking the very tables k_dict_regex would read and writing DictMatch
+// records through the same counter-and-capacity protocol: what the host side made of a pattern — DFA, premultiplied states, class tables,
+// alphabet — is then checked end to end without a GPU.
+void launch_dict_regex(hipStream_t, uint32_t char_bytes, bool small_tables, const RegexProbeD* probes, const uint16_t* pool, const uint32_t* alpha, uint32_t n_alpha,
+                       uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const void* chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap,
+                       DictMatch* out) {
+    log_launch("k_dict_regex", {char_bytes, small_tables, n_alpha, probe_base, n_probes, num_terms, out_cap});
+    if (!std::getenv("VQ_STUB_DICT_SCAN")) {
+        no_device("k_dict_regex");
+        return;
+    }
+    for (uint32_t p = 0; p < n_probes; ++p) {
+        const RegexProbeD& P = probes[p];
+        const uint64_t lds = uint64_t(regex_words16(P.n_next, n_alpha)) * 2 + uint64_t(n_alpha) * 4;
+        if (lds > (small_tables ? vqregex::kLdsTableBytesSmall : vqregex::kLdsTableBytes) + 32u || P.start >= P.n_next)
+            throw vqreq::VelociError(vqreq::ERR_DEVICE, "k_dict_regex (stub): a probe whose tables the kernel would refuse");
+        const uint16_t* next = pool + P.tab_off;
+        const uint16_t* ascii = next + P.n_next;
+        const uint16_t* acls = ascii + 128;
+        for (uint32_t t = 0; t < num_terms; ++t) {
+            uint32_t state = P.start;
+            for (uint32_t i = off[t]; i < off[t + 1]; ++i) {
+                const uint32_t cp = char_bytes == 4 ? static_cast<const uint32_t*>(chars)[i] : static_cast<const uint16_t*>(chars)[i];
+                uint32_t c;
+                if (cp < 128u) c = ascii[cp];
+                else {
+                    uint32_t lo = 0, hi = n_alpha;
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (alpha[mid] < cp) lo = mid + 1u;
+                        else hi = mid;
+                    }
+                    c = lo < n_alpha ? acls[lo] : 0u;
+                }
+                if (state + c >= P.n_next) throw vqreq::VelociError(vqreq::ERR_DEVICE, "k_dict_regex (stub): a transition outside the table");
+                state = next[state + c];
+            }
+            if (state >= P.first_accept) {
+                const uint32_t pos = (*out_count)++;
+                if (pos < out_cap) out[pos] = DictMatch{probe_base + p, t, 0u};
+            }
+        }
+    }
+}
 }  // namespace vq
 
 extern "C" void vq_stub_fail_launches_after(long k) { vq::stub_set_fail_after(k); }

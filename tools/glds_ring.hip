@@ -1,5 +1,5 @@
 // LDS-DMA (global_load_lds_*) on gfx950: what the instruction does with its operands (part A), and what a loader-wave / consumer-wave
-// ring per CU streams (part B) — the skeleton of k_scan_ring (veloci_amd/csrc/scan_ring.hip), measured before that kernel was written.
+// ring per CU streams (part B) — the skeleton of k_scan_ring (veloci_amd/csrc/scan_ring.hip, retired: last in commit 3ee56ad), measured before that kernel was written.
 //
 //   hipcc --offload-arch=gfx950 -O3 tools/glds_ring.hip -o tools/glds_ring && tools/glds_ring
 //

@@ -2,8 +2,8 @@
 (tests/native/hip_stub.cpp) with VQ_STUB_NOOP_LAUNCH=1 — launches do nothing, "results" are garbage — runs compile, pack, the launch calls and the
 result assembly of 1024-request steps; VQ_TIMING prints where the time went.  A development aid; nothing here is a measurement of the product.
     g++ -std=c++17 -O2 -fPIC -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o /tmp/libveloci_host.so \
-        veloci_amd/csrc/{index,compile,exec,hostpool,capi}.cpp tests/native/hip_stub.cpp tests/native/hip_stub_dict_wide.cpp tests/native/hip_stub_probe_shapes.cpp \
-        tests/native/hip_stub_union_dense.cpp
+        veloci_amd/csrc/{index,compile,exec,hostpool,capi,regex_dfa}.cpp tests/native/hip_stub.cpp
+    (or `make -C veloci_amd/csrc hoststub`: veloci_amd/_host_stub/libveloci_host_stub.so, the same at -O1)
     python tools/host_step_profile.py /tmp/libveloci_host.so [single|and|mix] [steps]"""
 import os
 import sys

@@ -805,6 +805,7 @@ static void copy_flat(const std::vector<std::unique_ptr<Result>>& results, const
         if (r.ids.size() > stride) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "flat output: stride smaller than a request's top");
         num_hits[i] = r.num_hits;
         counts[i] = uint32_t(r.ids.size());
+        if (r.ids.empty()) continue;  // (an empty vector's data() may be null: not an argument for memcpy)
         std::memcpy(ids + i * stride, r.ids.data(), r.ids.size() * 4);
         std::memcpy(scores + i * stride, r.scores.data(), r.scores.size() * 4);
     }
@@ -1440,7 +1441,6 @@ const char* vq_profile_json(const vq_index* i, int reset) {
 #ifdef VQ_STAMP
 void vq_debug_stamps(unsigned long long* out, int reset) { vq::debug_read_stamps(out, reset); }
 void vq_debug_probe_stamps(unsigned long long* out, int reset) { vq::debug_read_probe_stamps(out, reset); }
-void vq_debug_ring_stamps(unsigned long long* out, int reset) { vq::debug_read_ring_stamps(out, reset); }
 #endif
 
 }  // extern "C"

@@ -1758,21 +1758,21 @@ struct Compiler {
         for (uint32_t li = 0; li < cq.lists.size(); ++li)  // every list must be a leaf or a side list
             if (leaf_of(li) < 0 && std::find(sides.begin(), sides.end(), uint16_t(li)) == sides.end()) return;
         // flags as for the flat simple queries, per leaf
-        uint32_t f = (1u << 17) | (1u << 18);
+        uint32_t f = kSfSimple | kSfRich;
         bool seq = false;
         for (uint32_t k = 0; k < n; ++k) {
             const HList& l = cq.lists[leaves[k]];
             if ((l.flags & LIST_COVER) && (l.flags & LIST_BITMAP)) seq = true;
         }
-        if (seq) f |= 1u << 16;
+        if (seq) f |= kSfSeq;
         bool any_cover = false;
         for (uint32_t k = 0; k < n; ++k) {
             const HList& l = cq.lists[leaves[k]];
             const bool cover = l.flags & LIST_COVER;
             any_cover = any_cover || cover;
-            if (cover) f |= 1u << (8 + k);
-            if ((l.flags & LIST_BITMAP) && (seq || !cover)) f |= 1u << k;
-            if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (20 + k);
+            if (cover) f |= 1u << (kSfCoverShift + k);
+            if ((l.flags & LIST_BITMAP) && (seq || !cover)) f |= 1u << (kSfBitmapShift + k);
+            if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (kSfPrefetchShift + k);
         }
         if (!any_cover) return;
         rich_bounds(S, leaves, n);
@@ -1887,7 +1887,7 @@ struct Compiler {
         if (!any_cover) return;
         W.seq = seq ? 1 : 0;
         cq.wide = W;
-        cq.simple_flags = 1u << 24;
+        cq.simple_flags = kSfWide;
         cq.simple_n = 0;
     }
 
@@ -2233,7 +2233,7 @@ struct Compiler {
             const bool pure = cq.simple_n && count_reqs.empty() && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
                               cq.facets.empty() && uint64_t(idx.doc_hi) - idx.doc_lo >= 65536;
             if (pure && !force_generic) {
-                uint32_t f = 1u << 17;
+                uint32_t f = kSfSimple;
                 // An AND whose cover (sparsest operand) is ONE list with a tile directory (at least 1/4096 of the docs) and whose other operands
                 // all have bitmap images: k_scan_probe streams the cover's postings — as ids and scores, even when the cover has a bitmap
                 // image of its own — and tests their bits in the operands' LDS tiles (VQ_NO_PROBE=1: k_scan_simple instead).
@@ -2305,9 +2305,9 @@ struct Compiler {
                     const HList& l = cq.lists[cq.ops[k].list_begin];
                     if ((l.flags & LIST_COVER) && (l.flags & LIST_BITMAP)) seq = true;
                 }
-                if (seq) f |= 1u << 16;
+                if (seq) f |= kSfSeq;
                 if (probe) {
-                    f |= 1u << 25 | arr_mask << 12 | (or_probe ? 1u << 27 : 0u);
+                    f |= kSfProbe | arr_mask << kSfArrayShift | (or_probe ? kSfProbeOr : 0u);
                     cq.probe = DProbe{};
                     for (uint32_t k = 0; k < cq.simple_n; ++k) {
                         const HList& l = cq.lists[cq.ops[k].list_begin];
@@ -2315,25 +2315,19 @@ struct Compiler {
                         if ((arr_mask >> k) & 1u) cq.probe_arr_gran = std::max(cq.probe_arr_gran, l.tile_most);
                     }
                 }
-                // ... and with top + skip <= 32 (the candidate buffer is one key per lane, the query has a shared pool) the persistent form of that
-                // kernel, k_scan_ring: loader waves stream the tiles into LDS rings, consumer waves probe (opt-in)
-                // Measured on launches that read no list twice (256 distinct queries per launch, 100 M docs): 1.95 ms against k_scan_probe's 1.94 —
-                // the stream side reaches 5.9 TB/s alone, the consumer waves do not keep up: opt-in, VQ_RING=1
-                static const bool ring = std::getenv("VQ_RING") != nullptr && std::atoi(std::getenv("VQ_RING")) != 0;
-                if (probe && ring && !arr_mask && !or_probe && cq.top_k >= 1 && cq.top_k <= kPoolMaxK) f |= 1u << 26;
                 for (uint32_t k = 0; k < cq.simple_n; ++k) {
                     const HList& l = cq.lists[cq.ops[k].list_begin];
                     const bool cover = or_probe ? k == or_cover : (l.flags & LIST_COVER) != 0;
-                    if (cover) f |= 1u << (8 + k);
-                    if ((l.flags & LIST_BITMAP) && (seq || !cover) && !((arr_mask >> k) & 1u)) f |= 1u << k;
-                    if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (20 + k);
+                    if (cover) f |= 1u << (kSfCoverShift + k);
+                    if ((l.flags & LIST_BITMAP) && (seq || !cover) && !((arr_mask >> k) & 1u)) f |= 1u << (kSfBitmapShift + k);
+                    if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (kSfPrefetchShift + k);
                 }
                 // a single leaf whose list has a tile-packed image: k_scan_union streams that (4 B per posting) instead of ids + scores (6 B)
                 static const bool no_union_cov = std::getenv("VQ_NO_UNION_COV") != nullptr;
                 if (cq.simple_n == 1 && !no_union_cov) {
                     const HList& l = cq.lists[cq.ops[0].list_begin];
                     if (l.d_cov32 && l.d_gdir && l.d_tile_dir && l.term_score > 0.0f && !(l.flags & LIST_F32) && l.inline_idx < 0) {
-                        f |= 1u << 28;
+                        f |= kSfUnionPacked;
                         cq.probe = DProbe{};
                         cq.probe.leaf[0] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
                     }
@@ -2348,12 +2342,13 @@ struct Compiler {
                 (cq.lists[cq.ops[0].list_begin].flags & LIST_F32) && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
                 cq.facets.empty())  // (with facets the rich kernel is faster: its 64-hit rounds put less pressure on the histogram's hot counters
                                     //  than every span adding at once — an LDS-privatised histogram would lift that)
-                cq.simple_flags = 1u << 19;
+                cq.simple_flags = kSfLeafF32;
         }
         if (!cq.simple_flags) detect_rich_simple();
         if (!cq.simple_flags) detect_wide();
-        if (!cq.simple_flags || ((cq.simple_flags >> 24) & 1u)) compute_prune_table();
-        if (!cq.simple_flags && count_reqs.empty()) {  // k_tile_scan: a dense cover list means every tile gets visited anyway: walk them in order
+        cq.kclass = route_query(cq);  // simple_flags is final: everything below — and the launch (exec.cpp) — goes by the class
+        if (cq.kclass == K_TILE_SCAN || cq.kclass == K_SCAN_WIDE) compute_prune_table();
+        if (cq.kclass == K_TILE_SCAN && count_reqs.empty()) {  // k_tile_scan: a dense cover list means every tile gets visited anyway: walk them in order
             bool dense_cover = false;                   // and read the dense lists as bitmap images instead of scattering them
             for (auto& l : cq.lists) dense_cover = dense_cover || ((l.flags & LIST_COVER) && (l.flags & LIST_BITMAP));
             if (dense_cover) {
@@ -2384,15 +2379,22 @@ struct Compiler {
             const char* e = std::getenv("VQ_SPAN_POSTINGS");
             return uint64_t(e ? std::atoll(e) : 0);
         }();
-        const bool and_like = ((cq.simple_flags >> 18) & 1u) || (cq.simple_flags && cq.simple_n > 1 && cq.ops.back().kind == OP_AND);  // rich, or a plain simple AND
-        const bool wide_like = (cq.simple_flags >> 24) & 1u;  // k_scan_wide: its count-class pruning gains most from a long warm-up (OR over 8 terms: 27.6 k q/s at 256 Ki, 29.0 k at 512 Ki, 28.7 k at 1 Mi)
-        const bool probe_like = (cq.simple_flags >> 25) & 1u;  // k_scan_probe prunes by the query's shared threshold: long spans warm up once (launches of 512: 4.29 ms at 128 Ki, 3.77 ms at 1 Mi)
         // (on a small shard the same number of spans per query is kept — a 1/8 shard with 1 Mi-posting spans would leave half the chip without a wave)
         const uint64_t probe_span = std::min<uint64_t>(std::max<uint64_t>(range / 96, 131072), 1048576);
-        // a plain simple OR prunes by its threshold too: on a large shard longer spans warm up once (3-term OR on 100 M docs, launches of 1024: 9.99 ms at 256 Ki,
-        // 9.57 at 512 Ki, 9.64 at 1 Mi, 10.86 at 2 Mi); a small shard keeps the span count that fills the chip
-        const bool or_like = cq.simple_flags && !((cq.simple_flags >> 18) & 1u) && !wide_like && !probe_like && cq.simple_n > 1 && cq.ops.back().kind == OP_OR;
-        const uint64_t span_postings = span_env ? span_env : (probe_like ? probe_span : and_like ? 131072 : wide_like ? 589824 : (or_like && range >= 50'000'000ull) ? 524288 : 262144);  // (wide, launches of 512: 29.7-29.8 k requests/s at 512 Ki, 29.8-30.1 k at 576 Ki, 29.8 k at 608 Ki; AND of two 4-term ORs 30.7 -> 31.3 k)
+        uint64_t span_postings = 262144;
+        switch (sizing_class()) {
+            case K_SCAN_PROBE: span_postings = probe_span; break;  // k_scan_probe prunes by the query's shared threshold: long spans warm up once (launches of 512: 4.29 ms at 128 Ki, 3.77 ms at 1 Mi)
+            case K_SCAN_RICH:
+            case K_SCAN_AND: span_postings = 131072; break;
+            // k_scan_wide: its count-class pruning gains most from a long warm-up (OR over 8 terms: 27.6 k q/s at 256 Ki, 29.0 k at 512 Ki, 28.7 k at 1 Mi; launches of 512: 29.7-29.8 k
+            // requests/s at 512 Ki, 29.8-30.1 k at 576 Ki, 29.8 k at 608 Ki; AND of two 4-term ORs 30.7 -> 31.3 k)
+            case K_SCAN_WIDE: span_postings = 589824; break;
+            // a plain simple OR prunes by its threshold too: on a large shard longer spans warm up once (3-term OR on 100 M docs, launches of 1024: 9.99 ms at 256 Ki,
+            // 9.57 at 512 Ki, 9.64 at 1 Mi, 10.86 at 2 Mi); a small shard keeps the span count that fills the chip
+            case K_SCAN_SIMPLE: span_postings = (cq.simple_n > 1 && range >= 50'000'000ull) ? 524288 : 262144; break;
+            default: break;
+        }
+        if (span_env) span_postings = span_env;
         uint32_t ww = ww_max;  // W = 32 * ww docs
         const size_t TL = size_t(L) + cq.n_temps;
         while (ww > 64 && (size_t(ww) + TL * ww + size_t(L) * ww / 2) * 4 > var_budget) ww >>= 1;
@@ -2420,29 +2422,26 @@ struct Compiler {
                 if (l.flags & LIST_COVER) cover_len += l.len;
             const uint64_t visited = std::max<uint64_t>(std::min<uint64_t>(cover_len, tiles), 1);
             // (k_scan_simple batches its gathers across tiles; tiles with a lot of postings are bandwidth-, not latency-bound)
-            if (!cq.simple_flags && cq.total_len / visited < 1024) spans = std::max<uint64_t>(spans, visited / 16);
-            if (((cq.simple_flags >> 18) & 1u) && cq.total_len / visited < 1024) spans = std::max<uint64_t>(spans, visited / 64);  // rich: 16384-doc tiles, cheaper each
-        }
-        if ((cq.simple_flags >> 26) & 1u) {
-            // k_scan_ring: a persistent grid draws (query, span) items from a counter, span 0 of every query first: a span needs no length to
-            // warm its threshold up (the query's pool is warm after the first round) — short spans even out the end of the launch
-            static const uint64_t ring_tiles = [] {
-                const char* e = std::getenv("VQ_RING_SPAN_TILES");
-                return uint64_t(e ? std::max(1, std::atoi(e)) : 64);
-            }();
-            const uint64_t ptiles = std::max<uint64_t>((range + (1u << kProbeTileShift) - 1) >> kProbeTileShift, 1);
-            spans = (ptiles + ring_tiles - 1) / ring_tiles;
+            if (cq.kclass == K_TILE_SCAN && cq.total_len / visited < 1024) spans = std::max<uint64_t>(spans, visited / 16);
+            if (cq.kclass == K_SCAN_RICH && cq.total_len / visited < 1024) spans = std::max<uint64_t>(spans, visited / 64);  // rich: 16384-doc tiles, cheaper each
         }
         spans = std::min<uint64_t>(spans, tiles);
         spans = std::min<uint64_t>(std::max<uint64_t>(spans, 1), 4096);
         cq.n_spans = uint32_t(spans);
-        if ((cq.simple_flags >> 19) & 1u) {  // spans are slices of the list's ENTRIES: even work whatever the doc distribution
+        if (cq.kclass == K_SCAN_LEAF_F32) {  // spans are slices of the list's ENTRIES: even work whatever the doc distribution
             const uint64_t len = cq.lists[cq.ops[0].list_begin].len;
             cq.n_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(len / (cq.facets.empty() ? 16384 : 4096), 1), 4096));
         }
         cq.max_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(tiles, 1), 4096));
-        if ((cq.simple_flags >> 19) & 1u) cq.max_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(cq.lists[cq.ops[0].list_begin].len / 64, 1), 4096));
+        if (cq.kclass == K_SCAN_LEAF_F32) cq.max_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(cq.lists[cq.ops[0].list_begin].len / 64, 1), 4096));
         compute_layout_bytes(root.cover_len);
+    }
+
+    // The class whose span length and byte accounting a query gets: its own, but for an OR that VQ_UNION_OR=1 took to k_scan_union — that
+    // experiment sizes and accounts it as on the route it left.
+    KernelId sizing_class() const {
+        if (cq.kclass == K_SCAN_UNION && cq.simple_n > 1) return sf_probe(cq.simple_flags) ? K_SCAN_PROBE : K_SCAN_SIMPLE;
+        return cq.kclass;
     }
 
     // Bytes this data layout has to move for the query, as far as they are known before it runs (KernelProfile::layout_bytes; the
@@ -2450,38 +2449,41 @@ struct Compiler {
     // directory entry per tile, a scattered list 4 B per id, a streamed posting list 6 B per posting, a materialised leaf 8 B per entry.
     void compute_layout_bytes(uint64_t cover_len) {
         const uint64_t range = uint64_t(idx.doc_hi) - idx.doc_lo;
-        const bool simple = cq.simple_flags != 0;
-        const bool wide = (cq.simple_flags >> 24) & 1u;
-        const uint64_t tile_docs = wide ? 8192 : ((cq.simple_flags >> 25) & 1u) ? (1u << kProbeTileShift) : simple ? 16384 : uint64_t(cq.tile_words) << 5;
+        const KernelId kc = sizing_class();
+        const uint32_t f = cq.simple_flags;
+        const uint64_t tile_docs = kc == K_SCAN_WIDE ? 8192 : kc == K_SCAN_PROBE ? (1u << kProbeTileShift) : kc == K_TILE_SCAN ? uint64_t(cq.tile_words) << 5 : 16384;
         const uint64_t tiles = std::max<uint64_t>((range + tile_docs - 1) / tile_docs, 1);
-        const bool seq = wide ? cq.wide.seq != 0 : simple ? ((cq.simple_flags >> 16) & 1u) : cq.seq_tiles != 0;
+        const bool seq = kc == K_SCAN_WIDE ? cq.wide.seq != 0 : kc == K_TILE_SCAN ? cq.seq_tiles != 0 : sf_seq(f);
         const uint64_t visited = seq ? tiles : std::min<uint64_t>(std::max<uint64_t>(cover_len, 1), tiles);
         auto bitmap_cost = [&]() { return visited * (tile_docs / 8 + 4); };
         uint64_t b = 8ull * cq.top_k;
-        if ((cq.simple_flags >> 19) & 1u) b += 8ull * cq.lists[cq.ops[0].list_begin].len;  // k_scan_leaf_f32
-        else if (simple && !((cq.simple_flags >> 18) & 1u) && cq.simple_n == 1 && std::getenv("VQ_NO_UNION") == nullptr)
-            b += (((cq.simple_flags >> 28) & 1u) ? 4ull : 6ull) * cq.lists[cq.ops[0].list_begin].len;  // k_scan_union: ids and scores streamed, or the tile-packed words
-        else if (wide) {
-            for (uint32_t k = 0; k < cq.wide.n_leaves; ++k) b += ((cq.wide.bitmap_mask >> k) & 1u) ? bitmap_cost() : 4ull * cq.lists[cq.wide.leaf_list[k]].len;
-        } else if ((cq.simple_flags >> 25) & 1u) {  // k_scan_probe: the cover's tile-packed (id, score) words are streamed, a bitmap operand's tiles come with 64 rank entries, an array operand costs 2 B per posting
-            for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                const uint64_t len = cq.lists[cq.ops[k].list_begin].len;
-                b += ((cq.simple_flags >> k) & 1u) ? visited * (tile_docs / 8 + 4 * (tile_docs >> kRankShift)) : ((cq.simple_flags >> (12 + k)) & 1u) ? 2ull * len : 4ull * len;
-            }
-        } else if (simple) {
-            std::vector<bool> seen(cq.lists.size(), false);
-            const bool rich = (cq.simple_flags >> 18) & 1u;
-            for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                const uint32_t li = rich ? cq.simple2.leaf_list[k] : cq.ops[k].list_begin;
-                seen[li] = true;
-                b += ((cq.simple_flags >> k) & 1u) ? bitmap_cost() : 4ull * cq.lists[li].len;
-            }
-            for (uint32_t li = 0; li < cq.lists.size(); ++li)
-                if (!seen[li]) b += 4ull * cq.lists[li].len;  // side lists
-        } else {
-            for (auto& l : cq.lists) {
-                const bool as_bitmap = (l.flags & LIST_BITMAP) && !(l.flags & LIST_COVER);
-                b += as_bitmap ? bitmap_cost() : 4ull * l.len;
+        switch (kc) {
+            case K_SCAN_LEAF_F32: b += 8ull * cq.lists[cq.ops[0].list_begin].len; break;
+            case K_SCAN_UNION: b += (sf_union_packed(f) ? 4ull : 6ull) * cq.lists[cq.ops[0].list_begin].len; break;  // ids and scores streamed, or the tile-packed words
+            case K_SCAN_WIDE:
+                for (uint32_t k = 0; k < cq.wide.n_leaves; ++k) b += ((cq.wide.bitmap_mask >> k) & 1u) ? bitmap_cost() : 4ull * cq.lists[cq.wide.leaf_list[k]].len;
+                break;
+            case K_SCAN_PROBE:  // the cover's tile-packed (id, score) words are streamed, a bitmap operand's tiles come with 64 rank entries, an array operand costs 2 B per posting
+                for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                    const uint64_t len = cq.lists[cq.ops[k].list_begin].len;
+                    b += sf_bitmap(f, k) ? visited * (tile_docs / 8 + 4 * (tile_docs >> kRankShift)) : sf_array(f, k) ? 2ull * len : 4ull * len;
+                }
+                break;
+            case K_TILE_SCAN:
+                for (auto& l : cq.lists) {
+                    const bool as_bitmap = (l.flags & LIST_BITMAP) && !(l.flags & LIST_COVER);
+                    b += as_bitmap ? bitmap_cost() : 4ull * l.len;
+                }
+                break;
+            default: {  // k_scan_simple, plain or rich
+                std::vector<bool> seen(cq.lists.size(), false);
+                for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                    const uint32_t li = kc == K_SCAN_RICH ? cq.simple2.leaf_list[k] : cq.ops[k].list_begin;
+                    seen[li] = true;
+                    b += sf_bitmap(f, k) ? bitmap_cost() : 4ull * cq.lists[li].len;
+                }
+                for (uint32_t li = 0; li < cq.lists.size(); ++li)
+                    if (!seen[li]) b += 4ull * cq.lists[li].len;  // side lists
             }
         }
         for (auto& f : cq.facets) b += 4ull * f.num_values;
@@ -2490,6 +2492,26 @@ struct Compiler {
 };
 
 }  // namespace
+
+// THE routing decision: the scan kernel a compiled query runs on, from its final simple_flags.  The order of the tests is the precedence.  Span
+// sizing and byte accounting (above) and the launch plan (run_partial) go by the result; nothing else derives a class from the flag bits.
+KernelId route_query(const CompiledQuery& cq) {
+    // every posting is a hit: k_scan_union streams the scores with the doc ids.  Single leaves always (VQ_NO_UNION=1 turns it off); its two-pass OR
+    // is correct but not yet faster than the survivor queue of k_scan_simple (50 vs 40 ms per 256 3-term ORs on 100 M docs), so ORs take it only
+    // with VQ_UNION_OR=1
+    static const bool union_enabled = std::getenv("VQ_NO_UNION") == nullptr;
+    static const bool union_or = std::getenv("VQ_UNION_OR") != nullptr;
+    const uint32_t f = cq.simple_flags;
+    if (sf_leaf_f32(f)) return K_SCAN_LEAF_F32;
+    if (sf_wide(f)) return K_SCAN_WIDE;
+    if (sf_rich(f)) return K_SCAN_RICH;
+    if (!f) return K_TILE_SCAN;
+    const bool root_or = cq.ops.back().kind == OP_OR, root_and = cq.ops.back().kind == OP_AND;
+    if (union_enabled && (cq.simple_n == 1 || (union_or && root_or))) return K_SCAN_UNION;
+    if (sf_probe(f)) return K_SCAN_PROBE;
+    if (cq.simple_n > 1 && root_and) return K_SCAN_AND;
+    return K_SCAN_SIMPLE;
+}
 
 float default_score_for_distance_host(uint8_t distance, bool prefix_matches) { return default_score_for_distance(distance, prefix_matches); }
 size_t debug_sort_unique(uint32_t* ids, size_t n) {  // (tests: the three regimes of sort_unique_u32 against an independent sort)

@@ -24,7 +24,7 @@ constexpr int kMaxChildren = 16;    // children per AND/OR node (the query gener
 constexpr int kMaxLists = 64;       // lists per query in one launch
 constexpr int kMaxOps = 160;
 constexpr int kMaxSkipWhen = 4;
-constexpr uint32_t kTileDirShift = 14;  // tile directory of an id list: one entry per 16384 docs (the tile of k_scan_ring)
+constexpr uint32_t kTileDirShift = 14;  // tile directory of an id list: one entry per 16384 docs (the tile of k_scan_simple)
 constexpr uint32_t kProbeTileShift = 15;  // the tile of k_scan_probe: 32768 docs = every second directory entry
 constexpr uint32_t kRankShift = 9;  // rank directory of a dense list: one entry per 512 docs (16 bitmap words = one 64-byte sector)
 
@@ -180,7 +180,7 @@ struct QHeader {
     uint32_t desc_bytes;     // leading part of the blob that the kernel stages into LDS (everything but inline lists)
     uint32_t n_pres, off_pres, off_pres_in, n_temps;
     uint32_t off_loc_idx;    // u16 list indices referenced by the identity-column DLocFields
-    uint32_t off_simple2;    // DSimple2 (simple_flags bit 18) or DWide (simple_flags bit 24)
+    uint32_t off_simple2;    // DSimple2 (kSfRich), DWide (kSfWide) or DProbe (kSfProbe, kSfUnionPacked)
     uint32_t off_pool;       // != 0: the query's shared top-k pool (DPool + top_k keys), written by the spans of k_scan_probe
     uint32_t prune_n;        // k_tile_scan top-k pruning: != 0: number of lists in prune_mask; a doc present in k of them scores at most
                              // unorder(prune_gbits[k]) (monotone in k), so docs with too few of them are counted as hits but never scored
@@ -197,17 +197,42 @@ struct QHeader {
                              // counts[part_keys_off + c] (the buffer passed as `num_hits`); nothing is scored
     uint32_t bitmap_base;    // doc id of bit 0 of every list bitmap of this shard (multiple of 65536)
     uint32_t simple_n;       // != 0: the score tree is simple_n single-list posting leaves under one AND/OR (or a single leaf)
-    uint32_t simple_flags;   // bits 0-3: leaf k is read as a bitmap; bits 8-11: leaf k is in the cover; bit 16: tiles are
-                             // visited sequentially (a dense list is in the cover); bit 17: eligible for k_scan_simple;
-                             // bit 18: rich simple query (DSimple2); bit 19: one materialised leaf (k_scan_leaf_f32); bits 20-23: leaf k has enough
-                             // entries per tile to prefetch its next 1 KiB round; bit 24: wide query (DWide, k_scan_wide); bit 25: AND whose
-                             // cover is ONE id list and whose other leaves are bitmap images or 16-bit arrays per tile (k_scan_probe, DProbe);
-                             // bits 12-15: leaf k is probed as a 16-bit array; bit 28: a single leaf whose tile-packed image
-                             // k_scan_union streams (DProbe::leaf[0]); bit 27: the root is an OR (k_scan_probe_or: docs without the cover
-                             // are counted but not scored — CompiledQuery::or_skip_bound); bit 26: all operands bitmaps, top_k <= 32, opted in: k_scan_ring
+    uint32_t simple_flags;   // what the scan kernels need to know about the query's shape: the kSf* fields below (0: k_tile_scan interprets the programs)
 };
 
-// k_scan_probe's view of a leaf (simple_flags bit 25; at QHeader::off_simple2): the tile-packed image of its posting list — the list's
+// ---- the fields of QHeader::simple_flags (CompiledQuery::simple_flags on the host).  Four masks with bit k = leaf k of a simple query ...
+constexpr uint32_t kSfBitmapShift = 0;     // leaf k is read as a bitmap image
+constexpr uint32_t kSfCoverShift = 8;      // leaf k is in the cover
+constexpr uint32_t kSfArrayShift = 12;     // k_scan_probe: leaf k is probed as a 16-bit array per tile
+constexpr uint32_t kSfPrefetchShift = 20;  // leaf k has enough entries per tile to prefetch its next 1 KiB round
+constexpr uint32_t kSfLeafMask = 0xFu;
+// ... and single bits
+constexpr uint32_t kSfSeq = 1u << 16;          // tiles are visited sequentially (a dense list is in the cover)
+constexpr uint32_t kSfSimple = 1u << 17;       // eligible for k_scan_simple: <= 4 single-list posting leaves under one AND / OR, nothing else
+constexpr uint32_t kSfRich = 1u << 18;         // rich simple query (DSimple2)
+constexpr uint32_t kSfLeafF32 = 1u << 19;      // one materialised leaf (k_scan_leaf_f32)
+constexpr uint32_t kSfWide = 1u << 24;         // wide query (DWide, k_scan_wide)
+constexpr uint32_t kSfProbe = 1u << 25;        // AND whose cover is ONE id list and whose other leaves are bitmap images or 16-bit arrays per tile (k_scan_probe, DProbe)
+//                 1u << 26                       reserved (was k_scan_ring)
+constexpr uint32_t kSfProbeOr = 1u << 27;      // with kSfProbe: the root is an OR (k_scan_probe_or: docs without the cover are counted but not scored — CompiledQuery::or_skip_bound)
+constexpr uint32_t kSfUnionPacked = 1u << 28;  // a single leaf whose tile-packed image k_scan_union streams (DProbe::leaf[0])
+__host__ __device__ inline uint32_t sf_bitmap_mask(uint32_t f) { return (f >> kSfBitmapShift) & kSfLeafMask; }
+__host__ __device__ inline uint32_t sf_cover_mask(uint32_t f) { return (f >> kSfCoverShift) & kSfLeafMask; }
+__host__ __device__ inline uint32_t sf_array_mask(uint32_t f) { return (f >> kSfArrayShift) & kSfLeafMask; }
+__host__ __device__ inline uint32_t sf_prefetch_mask(uint32_t f) { return (f >> kSfPrefetchShift) & kSfLeafMask; }
+__host__ __device__ inline bool sf_bitmap(uint32_t f, uint32_t k) { return (f >> (kSfBitmapShift + k)) & 1u; }
+__host__ __device__ inline bool sf_cover(uint32_t f, uint32_t k) { return (f >> (kSfCoverShift + k)) & 1u; }
+__host__ __device__ inline bool sf_array(uint32_t f, uint32_t k) { return (f >> (kSfArrayShift + k)) & 1u; }
+__host__ __device__ inline bool sf_prefetch(uint32_t f, uint32_t k) { return (f >> (kSfPrefetchShift + k)) & 1u; }
+__host__ __device__ inline bool sf_seq(uint32_t f) { return (f & kSfSeq) != 0u; }
+__host__ __device__ inline bool sf_rich(uint32_t f) { return (f & kSfRich) != 0u; }
+__host__ __device__ inline bool sf_leaf_f32(uint32_t f) { return (f & kSfLeafF32) != 0u; }
+__host__ __device__ inline bool sf_wide(uint32_t f) { return (f & kSfWide) != 0u; }
+__host__ __device__ inline bool sf_probe(uint32_t f) { return (f & kSfProbe) != 0u; }
+__host__ __device__ inline bool sf_probe_or(uint32_t f) { return (f & kSfProbeOr) != 0u; }
+__host__ __device__ inline bool sf_union_packed(uint32_t f) { return (f & kSfUnionPacked) != 0u; }
+
+// k_scan_probe's view of a leaf (kSfProbe; at QHeader::off_simple2): the tile-packed image of its posting list — the list's
 // postings grouped by 32768-doc tile, every tile padded to a multiple of 8 entries (a granule) with all-ones entries.
 struct DProbeLeaf {
     const uint32_t* cov32;  // (doc - tile_lo) << 16 | f16 score: what the cover streams; an array operand's scores are gathered from here

@@ -430,7 +430,7 @@ constexpr int kWorkspaces = 4;  // batches in flight per index (host compile of 
 
 // Kernels the profiler accounts separately (vq_profile_json): the pre-passes, one entry per scan class, the merges.
 enum KernelId : int {
-    K_DICT_SCAN = 0, K_DICT_REGEX, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_RING, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
+    K_DICT_SCAN = 0, K_DICT_REGEX, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
     K_SCAN_WIDE, K_TILE_SCAN, K_MERGE_SPANS, K_FINALIZE, K_FACET_SELECT, K_LOCALITY, K_BOOST1N, K_COUNT_
 };
 extern const char* const kKernelNames[K_COUNT_];
@@ -647,15 +647,16 @@ struct CompiledQuery {
     std::vector<uint16_t> pres_in;
     uint32_t n_temps = 0;
     uint32_t simple_n = 0;
-    uint32_t simple_flags = 0;
+    uint32_t simple_flags = 0;          // QHeader::simple_flags (the kSf* fields, device_types.hpp)
+    KernelId kclass = K_TILE_SCAN;      // the scan kernel the query runs on (route_query, set once simple_flags is final)
     std::vector<DGroup> groups;
     std::vector<DTermBoost> tboosts;
     std::vector<DColBoost> cols;
     std::vector<DLocField> locf;
     std::vector<uint16_t> loc_idx;
-    DSimple2 simple2{};  // simple_flags bit 18
-    DWide wide{};        // simple_flags bit 24
-    DProbe probe{};      // simple_flags bit 25
+    DSimple2 simple2{};  // kSfRich
+    DWide wide{};        // kSfWide
+    DProbe probe{};      // kSfProbe, kSfUnionPacked
     uint32_t probe_arr_gran = 0;  // ... the most granules any of its array operands has in one tile (the launch sizes the operands' LDS slot by it)
     std::vector<DFacet> facets;
     std::vector<FacetOut> facet_out;
@@ -665,7 +666,7 @@ struct CompiledQuery {
     uint64_t algorithmic_bytes = 0;
     uint64_t layout_bytes = 0;   // static part of KernelProfile::layout_bytes for this query (set when the kernel route is known)
     uint64_t key_upper = ~0ull;  // QHeader::key_upper
-    // k_scan_probe_or (simple_flags bit 27) scores only the docs that hold the cover; a doc without it scores at most this (the OR formula on the
+    // k_scan_probe_or (kSfProbeOr) scores only the docs that hold the cover; a doc without it scores at most this (the OR formula on the
     // other operands' list maxima).  The finished request is exact if its k-th best key lies above: finish_batch checks and otherwise asks for a
     // second run without the short cut (Result::rerun_exact).  NaN: not such a query.
     float or_skip_bound = std::numeric_limits<float>::quiet_NaN();
@@ -674,6 +675,7 @@ struct CompiledQuery {
     uint32_t max_spans = 1;  // tiles of the query's doc range (<= 4096): a small batch splits its queries further, up to this (exec.cpp)
 };
 
+KernelId route_query(const CompiledQuery& cq);
 CompiledQuery compile_query(const Index& idx, const vqreq::Request& req, const FuzzyTable* fuzzy = nullptr, const UnionTable* unions = nullptr,
                             const QueryCounts* counts = nullptr, const RangeTable* ranges = nullptr, Boost1nCache* boost_cache = nullptr,
                             const LocalityTable* localities = nullptr);
@@ -731,7 +733,6 @@ struct PartialBatch {
     // device addresses inside the workspace
     const uint8_t* d_blobs = nullptr;
     const uint32_t* d_blob_off = nullptr;
-    const uint32_t* d_span_base = nullptr;
     const FacetJob* d_facet_jobs = nullptr;
     uint8_t* d_partial = nullptr;
     uint32_t total_spans = 0;

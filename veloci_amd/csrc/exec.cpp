@@ -40,7 +40,7 @@ static double now_ms() { return std::chrono::duration<double, std::milli>(std::c
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
-                                            "k_scan_simple<2,rich>", "k_scan_ring (AND)", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
+                                            "k_scan_simple<2,rich>", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
                                             "k_merge_spans", "k_finalize", "k_facet_select", "k_locality", "k_boost1n"};
 
 LaunchTimer::LaunchTimer(bool on, Workspace& w, hipStream_t s, int kernel, uint64_t layout_bytes, uint64_t algorithmic_bytes, uint64_t queries) {
@@ -132,8 +132,8 @@ static size_t pack_blob(const CompiledQuery& cq, const Index& idx, uint8_t* dst,
     h.off_pres = uint32_t(section(cq.pres.size() * sizeof(DPresOp)));
     h.off_pres_in = uint32_t(section(cq.pres_in.size() * sizeof(uint16_t)));
     h.off_loc_idx = uint32_t(section(cq.loc_idx.size() * sizeof(uint16_t)));
-    h.off_simple2 = uint32_t(section((cq.simple_flags >> 18) & 1u ? sizeof(DSimple2) : (cq.simple_flags >> 24) & 1u ? sizeof(DWide) : ((cq.simple_flags >> 25) & 1u) || ((cq.simple_flags >> 28) & 1u) ? sizeof(DProbe) : 0));
-    const bool pool = ((cq.simple_flags >> 25) & 1u) && cq.top_k <= kPoolMaxK;
+    h.off_simple2 = uint32_t(section(sf_rich(cq.simple_flags) ? sizeof(DSimple2) : sf_wide(cq.simple_flags) ? sizeof(DWide) : sf_probe(cq.simple_flags) || sf_union_packed(cq.simple_flags) ? sizeof(DProbe) : 0));
+    const bool pool = sf_probe(cq.simple_flags) && cq.top_k <= kPoolMaxK;
     h.off_pool = pool ? uint32_t(section(sizeof(DPool) + 8 * size_t(cq.top_k))) : 0u;
     h.n_temps = cq.n_temps;
     h.n_counts = cq.n_counts;
@@ -186,9 +186,9 @@ static size_t pack_blob(const CompiledQuery& cq, const Index& idx, uint8_t* dst,
     if (!cq.cols.empty()) std::memcpy(dst + h.off_col, cq.cols.data(), cq.cols.size() * sizeof(DColBoost));
     if (!cq.locf.empty()) std::memcpy(dst + h.off_locf, cq.locf.data(), cq.locf.size() * sizeof(DLocField));
     if (!cq.loc_idx.empty()) std::memcpy(dst + h.off_loc_idx, cq.loc_idx.data(), cq.loc_idx.size() * sizeof(uint16_t));
-    if ((cq.simple_flags >> 18) & 1u) std::memcpy(dst + h.off_simple2, &cq.simple2, sizeof(DSimple2));
-    if ((cq.simple_flags >> 24) & 1u) std::memcpy(dst + h.off_simple2, &cq.wide, sizeof(DWide));
-    if (((cq.simple_flags >> 25) & 1u) || ((cq.simple_flags >> 28) & 1u)) std::memcpy(dst + h.off_simple2, &cq.probe, sizeof(DProbe));
+    if (sf_rich(cq.simple_flags)) std::memcpy(dst + h.off_simple2, &cq.simple2, sizeof(DSimple2));
+    if (sf_wide(cq.simple_flags)) std::memcpy(dst + h.off_simple2, &cq.wide, sizeof(DWide));
+    if (sf_probe(cq.simple_flags) || sf_union_packed(cq.simple_flags)) std::memcpy(dst + h.off_simple2, &cq.probe, sizeof(DProbe));
     if (!cq.pres.empty()) std::memcpy(dst + h.off_pres, cq.pres.data(), cq.pres.size() * sizeof(DPresOp));
     if (!cq.pres_in.empty()) std::memcpy(dst + h.off_pres_in, cq.pres_in.data(), cq.pres_in.size() * sizeof(uint16_t));
     DFacet* df = reinterpret_cast<DFacet*>(dst + h.off_facets);
@@ -1432,64 +1432,50 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     lay.off_hist = align_up(lay.off_keys + size_t(total_keys) * 8, 256);  // == bytes of the all-gathered part
     lay.bytes = align_up(lay.off_hist + size_t(total_hist) * 4, 256);
 
-    // ---- upload area: [blobs][blob_off][span_base][facet jobs]
+    // ---- upload area: [blobs][blob_off][span tables][qmap tables][facet jobs]
+    // One (span_base, qmap) table per scan launch, in launch order: span_base = prefix sums of n_spans over the launch's queries (and a closing
+    // entry), qmap = the blob slot of its k-th query.  The tables lie one behind the other, each as long as its launch has queries.
+    enum : uint32_t { T_LEAF_F32 = 0, T_RICH, T_PROBE, T_AND = T_PROBE + kProbeShapes, T_SIMPLE, T_UNION, T_WIDE, T_TILE, kScanTables };
+    struct ScanTable {
+        uint32_t first = 0;                       // of its entries inside the span / qmap areas
+        uint32_t *span_base = nullptr, *qmap = nullptr;  // host side of the upload area
+        uint32_t n = 0, spans = 0;                // queries, spans
+    } tabs[kScanTables];
+    auto table_of = [](const CompiledQuery& cq) -> uint32_t {
+        switch (cq.kclass) {
+            case K_SCAN_LEAF_F32: return T_LEAF_F32;
+            case K_SCAN_RICH: return T_RICH;
+            case K_SCAN_PROBE: {  // a kernel per shape: OR / AND of ND operands beside the cover, from ND = 2 on per number of array operands
+                if (sf_probe_or(cq.simple_flags)) return T_PROBE + kProbeOr;
+                const uint32_t nd = cq.simple_n - 1, na = uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
+                return T_PROBE + (nd <= 1 ? kProbeAnd1 : nd == 2 ? kProbeAnd2A0 + na : kProbeAnd3A0 + na);
+            }
+            case K_SCAN_AND: return T_AND;
+            case K_SCAN_SIMPLE: return T_SIMPLE;
+            case K_SCAN_UNION: return T_UNION;
+            case K_SCAN_WIDE: return T_WIDE;
+            case K_TILE_SCAN: return T_TILE;
+            default: throw VelociError(ERR_DEVICE, "query without a scan class (internal)");
+        }
+    };
     const size_t up_blob_off = align_up(blob_bytes, 256);
-    // two scan launches: pure simple queries (k_scan_simple) and everything else (k_tile_scan); each has its own
-    // span table (prefix sums of n_spans over its queries) and a map from its local query index to the blob slot
-    const size_t tbl = align_up(size_t(nq + 1) * 4, 256);
-    const size_t up_span_base = up_blob_off + tbl;   // generic: span_base_g
-    const size_t up_qmap_g = up_span_base + tbl;
-    const size_t up_span_s = up_qmap_g + tbl;
-    const size_t up_qmap_s = up_span_s + tbl;
-    const size_t up_span_d = up_qmap_s + tbl;   // every posting is a hit (single leaves): k_scan_union
-    const size_t up_qmap_d = up_span_d + tbl;
-    const size_t up_span_w = up_qmap_d + tbl;   // simple ANDs: k_scan_simple with 16384-doc tiles
-    const size_t up_qmap_w = up_span_w + tbl;
-    const size_t up_span_r = up_qmap_w + tbl;   // rich simple queries (DSimple2): k_scan_simple<2, true>
-    const size_t up_qmap_r = up_span_r + tbl;
-    const size_t up_span_f = up_qmap_r + tbl;   // one materialised leaf: k_scan_leaf_f32
-    const size_t up_qmap_f = up_span_f + tbl;
-    const size_t up_span_x = up_qmap_f + tbl;   // wide queries (DWide): k_scan_wide
-    const size_t up_qmap_x = up_span_x + tbl;
-    // ANDs (ORs) of one id-list cover and bitmap / array operands: k_scan_probe_*, a kernel per shape class with a table of its own.  The classes'
-    // tables lie one behind the other (class c: its queries + the closing entry of its span table), so all of them take one table's room + kProbeShapes entries
-    const size_t tbl_p = align_up(size_t(nq + 1 + kProbeShapes) * 4, 256);
-    const size_t up_span_p = up_qmap_x + tbl;
-    const size_t up_qmap_p = up_span_p + tbl_p;
-    const size_t up_qmap_n = up_qmap_p + tbl_p;   // ... with top + skip <= 32: k_scan_ring (a persistent grid: no span table, (query, span) items instead)
-    const size_t up_work_n = up_qmap_n + tbl;   // its item counter and error word (zeroed with every upload)
-    size_t ring_items_max = 0;                  // its item table: only when the launch's queries differ in their span counts
-    for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0 && ((pb->queries[i].simple_flags >> 26) & 1u)) ring_items_max += pb->queries[i].n_spans;
-    const size_t up_items_n = up_work_n + 256;
-    const size_t up_jobs = up_items_n + align_up(ring_items_max * 4, 256);
+    const size_t tbl = align_up(size_t(nq + kScanTables) * 4, 256);
+    const size_t up_span = up_blob_off + align_up(size_t(nq + 1) * 4, 256);
+    const size_t up_qmap = up_span + tbl;
+    const size_t up_jobs = up_qmap + tbl;
     const size_t up_bytes = up_jobs + align_up(jobs.size() * sizeof(FacetJob), 256) + 256;
     ws.h_up.ensure(up_bytes);
     ws.d_up.ensure(up_bytes);
     uint8_t* hup = ws.h_up.as<uint8_t>();
     uint8_t* dup = ws.d_up.as<uint8_t>();
-    bool union_has_or = false;
-    uint32_t scatter_wide = 0, scatter_simple = 0;  // id (scattered) lists per query: they alone need an LDS tile in k_scan_simple
-    uint32_t n_simple = 0, n_generic = 0, n_dense = 0, n_wide = 0, n_rich = 0, spans_simple = 0, spans_generic = 0, spans_dense = 0, spans_wide = 0, spans_rich = 0;
-    uint32_t scatter_rich = 0;
-    bool facets_rich = false;
-    uint32_t n_leaf = 0, spans_leaf = 0;
-    uint32_t n_xwide = 0, spans_xwide = 0, leaves_xwide = 0, scatter_xwide = 0;
-    struct ProbeClass {
-        uint32_t first = 0, n = 0, spans = 0;  // first: where the class's tables start inside the probe tables
-        uint32_t na_seen = 0, arr_slot = 0;    // bit NA: a query with NA array operands; words of an array operand's LDS slot (the fullest tile of the class's array lists)
-    } pcls[kProbeShapes];
-    auto probe_class = [](const CompiledQuery& cq) -> uint32_t {
-        if ((cq.simple_flags >> 27) & 1u) return kProbeOr;
-        const uint32_t nd = cq.simple_n - 1, na = uint32_t(__builtin_popcount((cq.simple_flags >> 12) & 0xFu));
-        return nd <= 1 ? kProbeAnd1 : nd == 2 ? kProbeAnd2A0 + na : kProbeAnd3A0 + na;
-    };
-    auto on_probe = [](const CompiledQuery& cq) {  // what the routing below may send to k_scan_probe_* (never fewer queries than it does: the tables are sized by this)
-        return cq.status == 0 && ((cq.simple_flags >> 25) & 1u) && !((cq.simple_flags >> 26) & 1u) && !((cq.simple_flags >> 19) & 1u) && !((cq.simple_flags >> 24) & 1u) &&
-               !((cq.simple_flags >> 18) & 1u);
-    };
+    // launch parameters, collected over each class's queries
+    bool union_has_or = false, facets_rich = false;
+    uint32_t scatter_and = 0, scatter_simple = 0, scatter_rich = 0;  // id (scattered) lists per query: they alone need an LDS tile in k_scan_simple
+    uint32_t leaves_wide = 0, scatter_wide = 0;
+    struct ProbeParams {
+        uint32_t na_seen = 0, arr_slot = 0;  // bit NA: a query with NA array operands; words of an array operand's LDS slot (the fullest tile of the shape's array lists)
+    } probe[kProbeShapes];
     bool any_probe = false;
-    uint32_t n_ring = 0, items_ring = 0, nd_ring = 1, ring_spans_each = 0;
     uint64_t cls_layout[K_COUNT_] = {}, cls_algo[K_COUNT_] = {}, cls_q[K_COUNT_] = {};
     {
         size_t off = 0;
@@ -1504,150 +1490,59 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
             if (packed != cq.blob_bytes) throw VelociError(ERR_DEVICE, "query blob changed size between compilation and packing (internal)");
             off += packed;
             ++qi;
+            ++tabs[table_of(cq)].n;  // pass 1: how many queries every table holds
         }
         hbo[nq] = uint32_t(off);
-        uint32_t* sg = reinterpret_cast<uint32_t*>(hup + up_span_base);
-        uint32_t* mg = reinterpret_cast<uint32_t*>(hup + up_qmap_g);
-        uint32_t* ss = reinterpret_cast<uint32_t*>(hup + up_span_s);
-        uint32_t* ms = reinterpret_cast<uint32_t*>(hup + up_qmap_s);
-        uint32_t* sd = reinterpret_cast<uint32_t*>(hup + up_span_d);
-        uint32_t* md = reinterpret_cast<uint32_t*>(hup + up_qmap_d);
-        uint32_t* sw = reinterpret_cast<uint32_t*>(hup + up_span_w);
-        uint32_t* mw = reinterpret_cast<uint32_t*>(hup + up_qmap_w);
-        uint32_t* sr = reinterpret_cast<uint32_t*>(hup + up_span_r);
-        uint32_t* mr = reinterpret_cast<uint32_t*>(hup + up_qmap_r);
-        uint32_t* sf = reinterpret_cast<uint32_t*>(hup + up_span_f);
-        uint32_t* mf = reinterpret_cast<uint32_t*>(hup + up_qmap_f);
-        uint32_t accf = 0, accx = 0;
-        uint32_t* sx = reinterpret_cast<uint32_t*>(hup + up_span_x);
-        uint32_t* mx = reinterpret_cast<uint32_t*>(hup + up_qmap_x);
-        uint32_t accg = 0, accs = 0, accd = 0, accw = 0, accr = 0;
-        uint32_t* sp = reinterpret_cast<uint32_t*>(hup + up_span_p);
-        uint32_t* mp = reinterpret_cast<uint32_t*>(hup + up_qmap_p);
-        {  // how many queries every probe class holds: where its tables start
-            uint32_t cnt[kProbeShapes] = {};
-            for (size_t i = 0; i < n; ++i)
-                if (on_probe(pb->queries[i])) ++cnt[probe_class(pb->queries[i])];
-            uint32_t at = 0;
-            for (uint32_t c = 0; c < kProbeShapes; ++c) {
-                pcls[c].first = at;
-                at += cnt[c] + 1;
-            }
+        uint32_t at = 0;
+        for (ScanTable& t : tabs) {  // ... which places them
+            t.first = at;
+            t.span_base = reinterpret_cast<uint32_t*>(hup + up_span) + at;
+            t.qmap = reinterpret_cast<uint32_t*>(hup + up_qmap) + at;
+            at += t.n + 1;
+            t.n = 0;
         }
-        uint32_t* mn = reinterpret_cast<uint32_t*>(hup + up_qmap_n);
-        uint32_t ring_max_spans = 0;
-        std::vector<uint32_t> ring_ns;  // spans of k_scan_ring's queries
-        bool ring_uniform = true;
-        std::memset(hup + up_work_n, 0, 256);
         qi = 0;
-        for (size_t i = 0; i < n; ++i) {
+        for (size_t i = 0; i < n; ++i) {  // pass 2: the tables' entries and the launch parameters
             const CompiledQuery& cq = pb->queries[i];
             if (cq.status != 0) continue;
-            // every posting is a hit: k_scan_union streams the scores with the doc ids.  Single leaves always (VQ_NO_UNION=1 turns it
-            // off); its two-pass OR is correct but not yet faster than the survivor queue of k_scan_simple (50 vs 40 ms per 256
-            // 3-term ORs on 100 M docs), so ORs take it only with VQ_UNION_OR=1
-            static const bool union_enabled = std::getenv("VQ_NO_UNION") == nullptr;
-            static const bool union_or = std::getenv("VQ_UNION_OR") != nullptr;
-            const bool rich = (cq.simple_flags >> 18) & 1u;
-            const bool dense = !rich && union_enabled && cq.simple_flags && (cq.simple_n == 1 || (union_or && cq.ops.back().kind == OP_OR));
-            int kclass;
-            if ((cq.simple_flags >> 19) & 1u) {
-                kclass = K_SCAN_LEAF_F32;
-                sf[n_leaf] = accf;
-                mf[n_leaf++] = qi;
-                accf += cq.n_spans;
-            } else if ((cq.simple_flags >> 24) & 1u) {
-                kclass = K_SCAN_WIDE;
-                leaves_xwide = std::max<uint32_t>(leaves_xwide, cq.wide.n_leaves);
-                scatter_xwide = std::max<uint32_t>(scatter_xwide, cq.wide.n_leaves - uint32_t(__builtin_popcount(cq.wide.bitmap_mask)));
-                sx[n_xwide] = accx;
-                mx[n_xwide++] = qi;
-                accx += cq.n_spans;
-            } else if (rich) {
-                kclass = K_SCAN_RICH;
-                facets_rich = facets_rich || !cq.facets.empty();
-                scatter_rich = std::max<uint32_t>(scatter_rich, cq.simple_n - uint32_t(__builtin_popcount(cq.simple_flags & 0xFu)) + cq.simple2.n_side);
-                sr[n_rich] = accr;
-                mr[n_rich++] = qi;
-                accr += cq.n_spans;
-            } else if (dense) {
-                kclass = K_SCAN_UNION;
-                union_has_or = union_has_or || cq.simple_n > 1;
-                sd[n_dense] = accd;
-                md[n_dense++] = qi;
-                accd += cq.n_spans;
-            } else if ((cq.simple_flags >> 26) & 1u) {
-                kclass = K_SCAN_RING;
-                nd_ring = std::max<uint32_t>(nd_ring, cq.simple_n - 1);
-                ring_uniform = ring_uniform && (n_ring == 0 || cq.n_spans == ring_max_spans);
-                ring_max_spans = std::max(ring_max_spans, cq.n_spans);
-                mn[n_ring++] = qi;
-                ring_ns.push_back(cq.n_spans);
-                items_ring += cq.n_spans;
-            } else if ((cq.simple_flags >> 25) & 1u) {
-                kclass = K_SCAN_PROBE;
-                if (!on_probe(cq)) throw VelociError(ERR_DEVICE, "probe query outside the probe tables (internal)");
-                ProbeClass& pc = pcls[probe_class(cq)];
-                pc.na_seen |= 1u << uint32_t(__builtin_popcount((cq.simple_flags >> 12) & 0xFu));
-                pc.arr_slot = std::max(pc.arr_slot, cq.probe_arr_gran * 4u);
-                sp[pc.first + pc.n] = pc.spans;
-                mp[pc.first + pc.n++] = qi;
-                pc.spans += cq.n_spans;
-                any_probe = true;
-            } else if (cq.simple_flags && cq.simple_n > 1 && cq.ops.back().kind == OP_AND) {
-                kclass = K_SCAN_AND;
-                scatter_wide = std::max<uint32_t>(scatter_wide, cq.simple_n - uint32_t(__builtin_popcount(cq.simple_flags & 0xFu)));
-                sw[n_wide] = accw;
-                mw[n_wide++] = qi;
-                accw += cq.n_spans;
-            } else if (cq.simple_flags) {
-                kclass = K_SCAN_SIMPLE;
-                scatter_simple = std::max<uint32_t>(scatter_simple, cq.simple_n - uint32_t(__builtin_popcount(cq.simple_flags & 0xFu)));
-                ss[n_simple] = accs;
-                ms[n_simple++] = qi;
-                accs += cq.n_spans;
-            } else {
-                kclass = K_TILE_SCAN;
-                sg[n_generic] = accg;
-                mg[n_generic++] = qi;
-                accg += cq.n_spans;
+            const uint32_t ti = table_of(cq);
+            ScanTable& t = tabs[ti];
+            t.span_base[t.n] = t.spans;
+            t.qmap[t.n++] = qi;
+            t.spans += cq.n_spans;
+            const uint32_t n_scatter = cq.simple_n - uint32_t(__builtin_popcount(sf_bitmap_mask(cq.simple_flags)));
+            switch (cq.kclass) {
+                case K_SCAN_WIDE:
+                    leaves_wide = std::max<uint32_t>(leaves_wide, cq.wide.n_leaves);
+                    scatter_wide = std::max<uint32_t>(scatter_wide, cq.wide.n_leaves - uint32_t(__builtin_popcount(cq.wide.bitmap_mask)));
+                    break;
+                case K_SCAN_RICH:
+                    facets_rich = facets_rich || !cq.facets.empty();
+                    scatter_rich = std::max<uint32_t>(scatter_rich, n_scatter + cq.simple2.n_side);
+                    break;
+                case K_SCAN_UNION: union_has_or = union_has_or || cq.simple_n > 1; break;
+                case K_SCAN_PROBE: {
+                    ProbeParams& pp = probe[ti - T_PROBE];
+                    pp.na_seen |= 1u << uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
+                    pp.arr_slot = std::max(pp.arr_slot, cq.probe_arr_gran * 4u);
+                    any_probe = true;
+                    break;
+                }
+                case K_SCAN_AND: scatter_and = std::max(scatter_and, n_scatter); break;
+                case K_SCAN_SIMPLE: scatter_simple = std::max(scatter_simple, n_scatter); break;
+                default: break;
             }
-            pb->qclass.push_back(uint8_t(kclass));
-            cls_layout[kclass] += cq.layout_bytes;
-            cls_algo[kclass] += cq.algorithmic_bytes;
-            cls_q[kclass] += 1;
+            pb->qclass.push_back(uint8_t(cq.kclass));
+            cls_layout[cq.kclass] += cq.layout_bytes;
+            cls_algo[cq.kclass] += cq.algorithmic_bytes;
+            cls_q[cq.kclass] += 1;
             ++qi;
         }
-        sg[n_generic] = accg;
-        ss[n_simple] = accs;
-        sw[n_wide] = accw;
-        spans_wide = accw;
-        sr[n_rich] = accr;
-        spans_rich = accr;
-        sf[n_leaf] = accf;
-        spans_leaf = accf;
-        sx[n_xwide] = accx;
-        spans_xwide = accx;
-        for (const ProbeClass& pc : pcls) sp[pc.first + pc.n] = pc.spans;
-        if (n_ring) {  // k_scan_ring's items in round-major order: span 0 of every query, then span 1, ... (a query's pool is warm after its first span)
-            if (ring_uniform) ring_spans_each = ring_max_spans;
-            else {
-                uint32_t* it = reinterpret_cast<uint32_t*>(hup + up_items_n);
-                uint32_t k = 0;
-                for (uint32_t r = 0; r < ring_max_spans; ++r)
-                    for (uint32_t j = 0; j < n_ring; ++j)
-                        if (r < ring_ns[j]) it[k++] = (j << 12) | r;
-            }
-        }
-        sd[n_dense] = accd;
-        spans_generic = accg;
-        spans_simple = accs;
-        spans_dense = accd;
+        for (ScanTable& t : tabs) t.span_base[t.n] = t.spans;
         if (!jobs.empty()) std::memcpy(hup + up_jobs, jobs.data(), jobs.size() * sizeof(FacetJob));
     }
     pb->d_blobs = dup;
     pb->d_blob_off = reinterpret_cast<const uint32_t*>(dup + up_blob_off);
-    pb->d_span_base = reinterpret_cast<const uint32_t*>(dup + up_span_base);
     pb->d_facet_jobs = reinterpret_cast<const FacetJob*>(dup + up_jobs);
     if (nq == 0) return pb;
 
@@ -1678,7 +1573,7 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     bool facets_generic = false;  // k_tile_scan queries with facets: room for the LDS counter cache behind the descriptor
     static const bool no_facet_cache = std::getenv("VQ_NO_FACET_CACHE") != nullptr;
     for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0 && !pb->queries[i].simple_flags && !pb->queries[i].facets.empty()) facets_generic = !no_facet_cache;
+        if (pb->queries[i].status == 0 && pb->queries[i].kclass == K_TILE_SCAN && !pb->queries[i].facets.empty()) facets_generic = !no_facet_cache;
     if (facets_generic) desc_cap += 2 * 1024 * 4;
     static const uint32_t cand_min = [] {
         const char* e = std::getenv("VQ_CAND_CAP");  // (a small buffer is pruned — and its threshold raised — sooner: 64 beats 256 by 2-7 %, 32 beats 64 by 1-2 %)
@@ -1689,73 +1584,63 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     const uint32_t list_table = (std::max<uint32_t>(max_lists, 2) + 1u) & ~1u;  // k_tile_scan sizes its per-list LDS arrays to the launch's longest list table
     static const bool tile_queue = std::getenv("VQ_NO_QUEUE") == nullptr;  // k_tile_scan: survivors of several tiles share a scoring round
     for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0 && !pb->queries[i].simple_flags)
+        if (pb->queries[i].status == 0 && pb->queries[i].kclass == K_TILE_SCAN)
             lds_bytes = std::max(lds_bytes, tile_scan_lds_bytes(uint32_t(pb->queries[i].lists.size()) + pb->queries[i].n_temps, uint32_t(pb->queries[i].lists.size()), pb->queries[i].tile_words, stack_depth, cand_cap, desc_cap, tile_queue && !pb->queries[i].simple_n, list_table));
     if (lds_bytes > 160 * 1024) throw VelociError(ERR_UNSUPPORTED, "LDS tile larger than 160 KiB");
     const bool prof = pb->profiled;
     auto hits_ptr = reinterpret_cast<unsigned long long*>(pb->d_partial + lay.off_hits);
     auto hist_ptr = reinterpret_cast<uint32_t*>(pb->d_partial + lay.off_hist);
     auto keys_ptr = ws.d_span_keys.as<unsigned long long>();
-    auto tab = [&](size_t o) { return reinterpret_cast<const uint32_t*>(dup + o); };
-    if (spans_leaf) {
-        LaunchTimer t(prof, ws, st, K_SCAN_LEAF_F32, cls_layout[K_SCAN_LEAF_F32], cls_algo[K_SCAN_LEAF_F32], cls_q[K_SCAN_LEAF_F32]);
-        launch_scan_leaf_f32(st, spans_leaf, pb->d_blobs, pb->d_blob_off, tab(up_span_f), tab(up_qmap_f), n_leaf, cand_cap, keys_ptr, hits_ptr, hist_ptr);
+    auto d_span = [&](const ScanTable& t) { return reinterpret_cast<const uint32_t*>(dup + up_span) + t.first; };
+    auto d_qmap = [&](const ScanTable& t) { return reinterpret_cast<const uint32_t*>(dup + up_qmap) + t.first; };
+    auto timer = [&](int k) { return LaunchTimer(prof, ws, st, k, cls_layout[k], cls_algo[k], cls_q[k]); };
+    if (const ScanTable& t = tabs[T_LEAF_F32]; t.spans) {
+        auto lt = timer(K_SCAN_LEAF_F32);
+        launch_scan_leaf_f32(st, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_rich) {
-        LaunchTimer t(prof, ws, st, K_SCAN_RICH, cls_layout[K_SCAN_RICH], cls_algo[K_SCAN_RICH], cls_q[K_SCAN_RICH]);
-        launch_scan_simple(st, true, scatter_rich, spans_rich, pb->d_blobs, pb->d_blob_off, tab(up_span_r), tab(up_qmap_r), n_rich, cand_cap, keys_ptr, hits_ptr, hist_ptr, facets_rich);
-    }
-    VQ_HIP(hipGetLastError());
-    if (items_ring) {
-        static const uint32_t cus = [] {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-            return uint32_t(v);
-        }();
-        LaunchTimer t(prof, ws, st, K_SCAN_RING, cls_layout[K_SCAN_RING], cls_algo[K_SCAN_RING], cls_q[K_SCAN_RING]);
-        launch_scan_ring(st, nd_ring, cus, pb->d_blobs, pb->d_blob_off, tab(up_qmap_n), n_ring, ring_spans_each, tab(up_items_n), items_ring,
-                         reinterpret_cast<uint32_t*>(dup + up_work_n), keys_ptr, hits_ptr);
+    if (const ScanTable& t = tabs[T_RICH]; t.spans) {
+        auto lt = timer(K_SCAN_RICH);
+        launch_scan_simple(st, true, scatter_rich, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr, facets_rich);
     }
     VQ_HIP(hipGetLastError());
     if (any_probe) {  // (one timer over the shape kernels: the profile class is the sum of them)
-        LaunchTimer t(prof, ws, st, K_SCAN_PROBE, cls_layout[K_SCAN_PROBE], cls_algo[K_SCAN_PROBE], cls_q[K_SCAN_PROBE]);
+        auto lt = timer(K_SCAN_PROBE);
         static const bool trace = std::getenv("VQ_PROBE_TRACE") != nullptr;  // tools: what every shape kernel of a launch was given
         for (uint32_t c = 0; c < kProbeShapes; ++c)
-            if (pcls[c].spans && trace)
-                std::fprintf(stderr, "probe launch: shape %u, %u queries, %u spans, array slot %u words (fullest tile: %u granules), NA seen 0x%x\n", c, pcls[c].n, pcls[c].spans,
-                             pcls[c].arr_slot, pcls[c].arr_slot / 4, pcls[c].na_seen);
+            if (const ScanTable& t = tabs[T_PROBE + c]; t.spans && trace)
+                std::fprintf(stderr, "probe launch: shape %u, %u queries, %u spans, array slot %u words (fullest tile: %u granules), NA seen 0x%x\n", c, t.n, t.spans,
+                             probe[c].arr_slot, probe[c].arr_slot / 4, probe[c].na_seen);
         for (uint32_t c = 0; c < kProbeShapes; ++c)
-            if (pcls[c].spans)
-                launch_scan_probe_shape(st, c, pcls[c].na_seen, pcls[c].arr_slot, pcls[c].spans, pb->d_blobs, pb->d_blob_off, tab(up_span_p) + pcls[c].first, tab(up_qmap_p) + pcls[c].first,
-                                        pcls[c].n, cand_cap, keys_ptr, hits_ptr);
+            if (const ScanTable& t = tabs[T_PROBE + c]; t.spans)
+                launch_scan_probe_shape(st, c, probe[c].na_seen, probe[c].arr_slot, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_wide) {
-        LaunchTimer t(prof, ws, st, K_SCAN_AND, cls_layout[K_SCAN_AND], cls_algo[K_SCAN_AND], cls_q[K_SCAN_AND]);
-        launch_scan_simple(st, false, scatter_wide, spans_wide, pb->d_blobs, pb->d_blob_off, tab(up_span_w), tab(up_qmap_w), n_wide, cand_cap, keys_ptr, hits_ptr, hist_ptr);
+    if (const ScanTable& t = tabs[T_AND]; t.spans) {
+        auto lt = timer(K_SCAN_AND);
+        launch_scan_simple(st, false, scatter_and, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
     }
     VQ_HIP(hipGetLastError());
     // (16384-doc tiles pay off for ORs too once LDS no longer bounds the occupancy)
-    if (spans_simple) {
-        LaunchTimer t(prof, ws, st, K_SCAN_SIMPLE, cls_layout[K_SCAN_SIMPLE], cls_algo[K_SCAN_SIMPLE], cls_q[K_SCAN_SIMPLE]);
-        launch_scan_simple(st, false, scatter_simple, spans_simple, pb->d_blobs, pb->d_blob_off, tab(up_span_s), tab(up_qmap_s), n_simple, cand_cap, keys_ptr, hits_ptr, hist_ptr);
+    if (const ScanTable& t = tabs[T_SIMPLE]; t.spans) {
+        auto lt = timer(K_SCAN_SIMPLE);
+        launch_scan_simple(st, false, scatter_simple, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_dense) {
-        LaunchTimer t(prof, ws, st, K_SCAN_UNION, cls_layout[K_SCAN_UNION], cls_algo[K_SCAN_UNION], cls_q[K_SCAN_UNION]);
-        launch_scan_union(st, union_has_or, spans_dense, pb->d_blobs, pb->d_blob_off, tab(up_span_d), tab(up_qmap_d), n_dense, cand_cap, keys_ptr, hits_ptr);
+    if (const ScanTable& t = tabs[T_UNION]; t.spans) {
+        auto lt = timer(K_SCAN_UNION);
+        launch_scan_union(st, union_has_or, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_xwide) {
-        LaunchTimer t(prof, ws, st, K_SCAN_WIDE, cls_layout[K_SCAN_WIDE], cls_algo[K_SCAN_WIDE], cls_q[K_SCAN_WIDE]);
-        launch_scan_wide(st, leaves_xwide, scatter_xwide, spans_xwide, pb->d_blobs, pb->d_blob_off, tab(up_span_x), tab(up_qmap_x), n_xwide, cand_cap, keys_ptr, hits_ptr);
+    if (const ScanTable& t = tabs[T_WIDE]; t.spans) {
+        auto lt = timer(K_SCAN_WIDE);
+        launch_scan_wide(st, leaves_wide, scatter_wide, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (spans_generic) {
-        LaunchTimer t(prof, ws, st, K_TILE_SCAN, cls_layout[K_TILE_SCAN], cls_algo[K_TILE_SCAN], cls_q[K_TILE_SCAN]);
-        launch_tile_scan(st, spans_generic, lds_bytes, pb->d_blobs, pb->d_blob_off, pb->d_span_base, tab(up_qmap_g), n_generic, stack_depth, cand_cap, desc_cap, keys_ptr,
-                         hits_ptr, hist_ptr, tile_queue, list_table, facets_generic);
+    if (const ScanTable& t = tabs[T_TILE]; t.spans) {
+        auto lt = timer(K_TILE_SCAN);
+        launch_tile_scan(st, t.spans, lds_bytes, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, stack_depth, cand_cap, desc_cap, keys_ptr, hits_ptr, hist_ptr, tile_queue,
+                         list_table, facets_generic);
     }
     VQ_HIP(hipGetLastError());
     {
@@ -1768,7 +1653,7 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     if (timing_enabled())
         std::fprintf(stderr, "[vq timing] n=%zu compile %.3f ms (dictionary scans %.3f [%zu probes], pass 1 %.3f, unions %.3f [%zu jobs], pass 2 %.3f), range jobs %.3f [%zu], spans generic/simple/and/rich/union %u/%u/%u/%u/%u, pack+launch %.3f ms\n", n,
                      t_compiled - t_start, t_probes - t_start, fuzzy.size(), t_pass1 - t_probes, t_unions - t_pass1, unions.size(), t_compiled - t_ranges,
-                     t_ranges - t_unions, ranges.size(), spans_generic, spans_simple, spans_wide, spans_rich, spans_dense + spans_leaf, now_ms() - t_compiled);
+                     t_ranges - t_unions, ranges.size(), tabs[T_TILE].spans, tabs[T_SIMPLE].spans, tabs[T_AND].spans, tabs[T_RICH].spans, tabs[T_UNION].spans + tabs[T_LEAF_F32].spans, now_ms() - t_compiled);
     if (timing_enabled())
         std::fprintf(stderr, "[vq timing] pack+launch: span sizing + layout %.3f, blobs + tables %.3f, upload + launches %.3f ms\n", t_layout - t_compiled, t_packed - t_layout, now_ms() - t_packed);
     if (timing_enabled()) {  // thread-time inside compile_query since the last batch (all passes, all threads)

@@ -1824,7 +1824,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
     const uint32_t top_k = H->top_k;
     const DList* gl = reinterpret_cast<const DList*>(blob + H->off_lists);
     const DOp* gops = reinterpret_cast<const DOp*>(blob + H->off_ops);
-    const bool seq = (sflags >> 16) & 1u;
+    const bool seq = sf_seq(sflags);
     VQ_STAMP_INIT
     VQ_STAMP_COUNT(8)
     const DSimple2* S2 = reinterpret_cast<const DSimple2*>(blob + H->off_simple2);  // RICH only
@@ -1875,7 +1875,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
     uint32_t* bml = lds + kSLdsCand + 2 * cand_cap;  // [number of scattered (id) lists][SWW]: lists read as bitmap images need no LDS tile
     uint32_t bslot[4];                                // LDS tile of list k
 #pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) bslot[k] = (uint32_t)__popc(~sflags & ((1u << k) - 1u) & 0xFu) * SWW;
+    for (uint32_t k = 0; k < 4; ++k) bslot[k] = (uint32_t)__popc((~sflags >> kSfBitmapShift) & ((1u << k) - 1u) & kSfLeafMask) * SWW;
     CandState cs{cand, cand_n, thr, cand_cap, reinterpret_cast<unsigned long long*>(const_cast<uint8_t*>(blob) + offsetof(QHeader, gthr))};
     cs.upper = H->key_upper;
     uint32_t tiles_done = 0;
@@ -1891,7 +1891,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
     uint32_t cur[4] = {0, 0, 0, 0}, nxt[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
-        if (k < n && !((sflags >> k) & 1u)) {
+        if (k < n && !sf_bitmap(sflags, k)) {
             cur[k] = wave_lower_bound(lf[k].docs, lf[k].len, span_lo);
             nxt[k] = cur[k] < lf[k].len ? as_global(lf[k].docs)[cur[k]] : 0xFFFFFFFFu;
         }
@@ -1900,7 +1900,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
     const uint32_t* sdocs[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t slen[4] = {0, 0, 0, 0}, scur[4] = {0, 0, 0, 0}, snxt[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, sslot[4] = {0, 0, 0, 0};
     if constexpr (RICH) {
-        const uint32_t n_scatter = (uint32_t)__popc(~sflags & ((1u << n) - 1u) & 0xFu);
+        const uint32_t n_scatter = (uint32_t)__popc((~sflags >> kSfBitmapShift) & ((1u << n) - 1u) & kSfLeafMask);
 #pragma unroll
         for (uint32_t s = 0; s < 4; ++s)
             if (s < R.n_side) {
@@ -1941,7 +1941,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
         else {
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k)
-                if (k < n && ((sflags >> (8 + k)) & 1u)) head = nxt[k] < head ? nxt[k] : head;
+                if (k < n && sf_cover(sflags, k)) head = nxt[k] < head ? nxt[k] : head;
         }
         if (head >= span_hi) break;
         const uint32_t tile_lo = head & ~(SW - 1u);
@@ -1958,7 +1958,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
 #pragma unroll
             for (uint32_t h = 0; h < NV; ++h) wk[k][h] = kZero;
             if (k < n) {
-                if ((sflags >> k) & 1u) {
+                if (sf_bitmap(sflags, k)) {
                     const VQ_GLOBAL u32x4* gb = as_global(reinterpret_cast<const u32x4*>(lf[k].bitmap + ((tile_lo - bitmap_base) >> 5)));
 #pragma unroll
                     for (uint32_t h = 0; h < NV; ++h) wk[k][h] = gb[lane * NV + h];
@@ -1993,8 +1993,8 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
         }
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k)
-            if (k < n && !((sflags >> k) & 1u))
-                base_idx[k] = simple_scatter_list(lf[k].docs, lf[k].len, cur[k], nxt[k], bml + bslot[k], wk[k][0], (sflags >> (20 + k)) & 1u, tile_lo, tile_hi, lo_bound);
+            if (k < n && !sf_bitmap(sflags, k))
+                base_idx[k] = simple_scatter_list(lf[k].docs, lf[k].len, cur[k], nxt[k], bml + bslot[k], wk[k][0], sf_prefetch(sflags, k), tile_lo, tile_hi, lo_bound);
         if ((RICH ? R.prune != 0u : kind != OP_AND) && (tiles_done++ & 3u) == 0u && lane == 0) {  // (a plain AND has few survivors: nothing to prune; a rich query that prunes by bounds does, whatever its root) adopt the threshold other
                                                                           // spans of the query have published (QHeader::gthr)
             const unsigned long long g = *reinterpret_cast<volatile unsigned long long*>(cs.gthr);
@@ -2003,7 +2003,7 @@ __device__ __forceinline__ void scan_simple_body(const uint8_t* __restrict__ blo
         __syncthreads();  // one wave: LDS atomics above are ordered before the reads below
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k)
-            if (k < n && !((sflags >> k) & 1u)) {
+            if (k < n && !sf_bitmap(sflags, k)) {
 #pragma unroll
                 for (uint32_t h = 0; h < NV; ++h) wk[k][h] = reinterpret_cast<const u32x4*>(bml + bslot[k])[lane * NV + h];
             }
@@ -3672,7 +3672,7 @@ __global__ __launch_bounds__(64) void k_scan_union(const uint8_t* __restrict__ b
 
     const uint32_t n_spans = H->n_spans;
     const unsigned long long range = (unsigned long long)(H->doc_hi - H->doc_lo);
-    const bool cov_mode = n == 1u && ((H->simple_flags >> 28) & 1u) != 0u;  // the single leaf streams its tile-packed image (spans end on its tiles)
+    const bool cov_mode = n == 1u && sf_union_packed(H->simple_flags);  // the single leaf streams its tile-packed image (spans end on its tiles)
     const uint32_t span_mask = cov_mode ? ~((1u << kProbeTileShift) - 1u) : ~(kSW - 1u);
     const uint32_t span_lo = span == 0 ? H->doc_lo : ((H->doc_lo + (uint32_t)(range * span / n_spans)) & span_mask);
     const uint32_t span_hi = span + 1 == n_spans ? H->doc_hi : ((H->doc_lo + (uint32_t)(range * (span + 1) / n_spans)) & span_mask);

@@ -1,4 +1,4 @@
-// Pieces shared by the two AND-probe kernels (scan_probe.hip: one wave per span; scan_ring.hip: loader / consumer waves around LDS rings):
+// Pieces of the probe kernels (scan_probe.hip: one wave per span) that do not depend on how a kernel streams its tiles:
 // tile geometry, the query's arithmetic as it sits in LDS, the bound behind `raw_min`, the merge into the query's shared top-k pool.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -130,8 +130,8 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
     const uint16_t* d_arr[NA1];
     const uint32_t* d_agd[NA1];
     {
-        const uint32_t ck = (uint32_t)__ffs((int)((sflags >> 8) & 0xFu)) - 1u;
-        const uint32_t am = (sflags >> 12) & 0xFu;  // leaf k is an array operand (the host instantiates NA = their number)
+        const uint32_t ck = (uint32_t)__ffs((int)sf_cover_mask(sflags)) - 1u;
+        const uint32_t am = sf_array_mask(sflags);  // leaf k is an array operand (the host instantiates NA = their number)
         uint32_t role_of[4] = {0u, 0u, 0u, 0u};     // leaf k -> 0 = cover, 1 + i = operand i
         uint32_t ib = 0, ia = NB;
 #pragma unroll
@@ -756,7 +756,7 @@ __device__ __forceinline__ void probe_item(const uint32_t* __restrict__ span_bas
 
 VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_1(VQ_PROBE_PARAMS) {
     VQ_PROBE_ITEM
-    if (((as_const<QHeader>(blob)->simple_flags >> 12) & 0xFu) == 0u) probe_body<1, 0>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
+    if (sf_array_mask(as_const<QHeader>(blob)->simple_flags) == 0u) probe_body<1, 0>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
     else probe_body<1, 1>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
 }
 VQ_PROBE_KERNEL(VQ_PROBE_WAVES) k_scan_probe_2_0(VQ_PROBE_PARAMS) {
@@ -788,7 +788,7 @@ VQ_PROBE_KERNEL(3) k_scan_probe_3_3(VQ_PROBE_PARAMS) {
     probe_body<3, 3>(blob, span, q, cand_cap, arr_slot, span_keys, num_hits);
 }
 
-// The OR form of the same scan (simple_flags bit 27): an OR of 2 or 3 leaves with a term slot each whose sparsest operand streams as the cover
+// The OR form of the same scan (kSfProbeOr): an OR of 2 or 3 leaves with a term slot each whose sparsest operand streams as the cover
 // and whose other operands are bitmap words.  num_hits is the union: the set bits of the operands' ORed words plus the cover's postings
 // outside them.  Scored are the docs that hold the COVER — with whatever operands hold them too, each such set with its own bound.  Docs
 // WITHOUT the cover are counted, never scored: exact as long as none of them can reach the request's k-th best score — their scores are

@@ -215,8 +215,8 @@ void launch_dict_scan_wide(hipStream_t, uint32_t char_bytes, const DictProbeW*, 
     log_launch("k_dict_scan_wide", {char_bytes, probe_base, n_probes, num_terms, out_cap});
     no_device("k_dict_scan_wide");
 }
-// VQ_STUB_DICT_SCAN=1 (tools/host_profile.py only): exact / prefix probes answered by a plain loop, so that the host compiler can be timed on this
-// machine on requests with prefix leaves.  The sanitizer test leaves it off: there every launcher throws.
+// VQ_STUB_DICT_SCAN=1 (tools/host_profile.py; the pre-pass batch of tests/native/launch_plan_driver.py): exact / prefix probes answered by a plain
+// loop, so that requests with prefix leaves get through compile_batch (exec.cpp) without a GPU.  The sanitizer test leaves it off: there every launcher throws.
 void launch_dict_scan(hipStream_t, const DictProbe* probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const uint16_t* chars, const uint16_t* low_chars,
                       uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out) {
     log_launch("k_dict_scan", {probe_base, n_probes, num_terms, out_cap});

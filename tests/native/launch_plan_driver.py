@@ -1,7 +1,10 @@
 """Driver of the host-stub build for the launch plan (run by tests/test_launch_plan_cpu.py with VQ_LIB=<host-stub library>, VQ_STUB_NOOP_LAUNCH=1 and
 VQ_STUB_LAUNCH_LOG=<file>): one batch that reaches every scan class — on an unsharded index and on the two halves of a two-shard one — goes
 through compile, routing, table packing and the launch calls over a "device" whose launches do nothing but write down what they were given
-(tests/native/hip_stub.cpp).  The routing knobs are read once per process, so every environment leg is a run of its own."""
+(tests/native/hip_stub.cpp).  The routing knobs are read once per process, so every environment leg is a run of its own.
+With VQ_LAUNCH_PLAN_BATCH=prepass (and VQ_STUB_DICT_SCAN=1: the stub answers prefix probes with a plain loop) a second batch runs instead, on the
+same corpus: requests that go round the pre-pass loop of compile_batch (exec.cpp) — dictionary scan, union job, count pre-pass — beside plain
+ones that are compiled once."""
 import json
 import os
 import sys
@@ -45,6 +48,21 @@ def requests(meta):
     return reqs
 
 
+def prepass_requests(meta):
+    """a prefix leaf over every term of the dictionary (more than VQ_UNION_MIN of them have postings: a union job), alone and inside an AND; an AND
+    of ORs whose summation order follows run-time result sizes (count pre-pass); two plain requests that never come back for a second pass"""
+    t = dict(zip(DFS, meta.extra_probes))
+    tri = list(meta.triples[0])
+    leaf = lambda term, **more: {"search": dict({"path": "body", "terms": [term]}, **more)}
+    either = lambda *terms: {"or": {"queries": [leaf(x) for x in terms]}}
+    prefix = leaf("", starts_with=True)
+    return [synth.req_single(t["d1"]),
+            {"search_req": prefix, "top": 10},
+            {"search_req": {"and": {"queries": [prefix, leaf(t["d1"])]}}, "top": 10},
+            {"search_req": {"and": {"queries": [either(tri[0], tri[1]), either(t["d2"], t["a1"]), leaf(t["a3"])]}}, "top": 10},
+            synth.req_and([t["c"], t["d1"]])]
+
+
 def mark(what):
     with open(LOG, "a") as f:
         f.write(json.dumps({"section": what}) + "\n")
@@ -52,15 +70,20 @@ def mark(what):
 
 declined = []
 data, meta = synth.generate(spec, device="cpu")
-reqs = requests(meta)
+PREPASS = os.environ.get("VQ_LAUNCH_PLAN_BATCH") == "prepass"
+if PREPASS:
+    assert os.environ.get("VQ_STUB_DICT_SCAN") == "1"
+reqs = prepass_requests(meta) if PREPASS else requests(meta)
 for lo, hi in ((0, N), (0, N // 2), (N // 2, N)):
     idx = veloci_amd.Index(data, device=0, doc_lo=lo, doc_hi=hi)
     mark("docs [%d, %d)" % (lo, hi))
+    if PREPASS and hi - lo != N:
+        idx.set_allreduce(lambda values: None)  # the sums over the shards: the other shard adds nothing
     if hi - lo == N:
         res = veloci_amd.search_batch(reqs, idx, raise_on_error=False)
     else:
         res = veloci_amd.PartialBatch(idx, [veloci_amd.Request(r) for r in reqs]).merge(None, 1, raise_on_error=False)
     declined.append([i for i, r in enumerate(res) if isinstance(r, Exception)])
     del idx
-assert all(d == [len(reqs) - 1] for d in declined), declined
+assert all(d == ([] if PREPASS else [len(reqs) - 1]) for d in declined), declined
 print("LAUNCH_PLAN_DRIVER_OK " + json.dumps({"requests": len(reqs), "declined": declined}))

@@ -494,7 +494,7 @@ int vq_debug_compile(const vq_index* index, const vq_request* request) {
     int status = 0;
     const int rc = guard([&] {
         if (!index || !request) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_debug_compile: null argument");
-        vq::CompiledQuery cq = vq::compile_query(*index->idx, request->req, nullptr, nullptr, nullptr, nullptr, nullptr);
+        vq::CompiledQuery cq = vq::compile_query(*index->idx, request->req);
         status = cq.status;
         if (cq.status != 0) g_err = cq.error;
     });
@@ -687,6 +687,12 @@ uint32_t vq_suggest_term_id(const vq_suggest_result* r, size_t i) { return r->e[
 void vq_suggest_free(vq_suggest_result* r) { delete r; }
 
 // ------------------------------------------------------------------ search
+// the requests behind the handles of a batch (a null handle stays null: that request alone fails)
+static std::vector<const Request*> request_pointers(const vq_request* const* requests, size_t n) {
+    std::vector<const Request*> reqs(n);
+    for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+    return reqs;
+}
 // does the batch have pre-passes (dictionary scans of fuzzy / prefix leaves, then unions, range jobs ...)?  Their syncs make the host side of a
 // batch long; such batches are cut in two and run on two host threads (a sample decides: it is about the batch's character)
 static bool batch_has_prepasses(const std::vector<const Request*>& reqs) {
@@ -701,8 +707,7 @@ static bool batch_has_prepasses(const std::vector<const Request*>& reqs) {
     return false;
 }
 static int run_batch(const vq_index* index, const vq_request* const* requests, size_t n, vq_result** out, int* status, std::string* first_error) {
-    std::vector<const Request*> reqs(n);
-    for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+    const std::vector<const Request*> reqs = request_pointers(requests, n);
     std::vector<std::unique_ptr<Result>> results(n);
     std::vector<int> st(n, 0);
     std::vector<std::string> errs(n);
@@ -815,8 +820,7 @@ int vq_search_batch_flat(const vq_index* index, const vq_request* const* request
                          uint32_t* ids, float* scores, int* status) {
     return guard([&] {
         if (!index || (n && (!requests || !num_hits || !counts || !ids || !scores))) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_search_batch_flat: null argument");
-        std::vector<const Request*> reqs(n);
-        for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+        const std::vector<const Request*> reqs = request_pointers(requests, n);
         // Large batches run as a software pipeline of chunks over the index's two workspaces: while the GPU scans chunk c
         // the host compiles chunk c+1, and chunk c-1's merge + download run on the finish stream.
         bool any_deep = false;  // top + skip beyond one scan's ranking: such requests page on after their batch (not pipelined)
@@ -900,8 +904,7 @@ int vq_search_batch_partial(const vq_index* index, const vq_request* const* requ
     return guard([&] {
         if (!index || !out || (n && !requests)) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_search_batch_partial: null argument");
         *out = nullptr;
-        std::vector<const Request*> reqs(n);
-        for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+        const std::vector<const Request*> reqs = request_pointers(requests, n);
         auto pb = run_partial(*index->idx, reqs.data(), n);
         // on the index's own stream the packed buffer must be complete before another library (RCCL) reads it; on a
         // caller-provided stream the caller's collective is ordered behind the scan by the stream itself
@@ -918,8 +921,7 @@ int vq_search_batch_partial_at(const vq_index* index, const vq_request* const* r
         if (!index || !out || (n && !requests)) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_search_batch_partial_at: null argument");
         if (slot < 0 || slot >= vq::kWorkspaces) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_search_batch_partial_at: slot out of range");
         *out = nullptr;
-        std::vector<const Request*> reqs(n);
-        for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+        const std::vector<const Request*> reqs = request_pointers(requests, n);
         auto pb = run_partial(*index->idx, reqs.data(), n, slot, int64_t(arena_offset));
         if (index->idx->stream == index->idx->own_stream) VQ_HIP(hipStreamSynchronize(index->idx->stream));
         auto* h = new vq_partial_batch();
@@ -1261,8 +1263,7 @@ int vq_shard_step_begin(const vq_index* index, const vq_request* const* requests
         static const bool timing = std::getenv("VQ_TIMING") != nullptr;
         const auto tb0 = std::chrono::steady_clock::now();
         VQ_HIP(hipSetDevice(idx.device));
-        std::vector<const Request*> reqs(n);
-        for (size_t i = 0; i < n; ++i) reqs[i] = requests[i] ? &requests[i]->req : nullptr;
+        const std::vector<const Request*> reqs = request_pointers(requests, n);
         if (c.unmerged) {  // the step before this one: its merge goes out first, this step's scans run behind it
             vq_shard_step& prev = *static_cast<vq_shard_step*>(c.unmerged);
             step_queue_merge(prev);

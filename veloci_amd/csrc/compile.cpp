@@ -257,7 +257,7 @@ static void regex_objects(const RequestSearchPart& p, std::wregex& whole, std::w
     }
 }
 
-struct Compiler {
+struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cache, localities: the pass's pre-pass results)
     const Index& idx;
     const Request& req;
     CompiledQuery cq;
@@ -266,12 +266,6 @@ struct Compiler {
     std::map<std::string, std::map<std::string, std::vector<uint32_t>>> term_id_hits;  // path -> term -> term ids
     uint32_t max_depth = 0;
 
-    const FuzzyTable* fuzzy = nullptr;
-    const UnionTable* unions = nullptr;
-    const RangeTable* ranges = nullptr;
-    const LocalityTable* localities = nullptr;
-    Boost1nCache* boost_cache = nullptr;
-    const QueryCounts* counts = nullptr;
     uint32_t next_node = 0;
     std::vector<CountReq> count_reqs;   // operands whose result sizes a count pre-pass must measure
     std::vector<CountReq> maybe_reqs;   // ... only if some OR needs the label of a two-operand AND
@@ -280,7 +274,7 @@ struct Compiler {
     bool explain_on = false;                 // every leaf of the score tree carries options.explain (execution_plan.rs:46-85 after request.explain)
     std::shared_ptr<ExplainPlan> xplan;
 
-    Compiler(const Index& i, const Request& r, const FuzzyTable* f) : idx(i), req(r), fuzzy(f) {}
+    Compiler(const Index& i, const Request& r, const CompileInputs& in) : CompileInputs(in), idx(i), req(r) {}
 
     // ------------------------------------------------------------ explain plan
     int ex_leaf(const Leaf* l) {  // l == nullptr: the empty result of an and/or without operands
@@ -2525,7 +2519,7 @@ size_t debug_sort_unique(uint32_t* ids, size_t n) {  // (tests: the three regime
 // return_term and return_term_lowercase; the dictionary scan of a fuzzy / prefix part has run on the device (`fuzzy`).
 std::vector<SuggestEntry> suggest_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
     Request dummy;
-    Compiler c(idx, dummy, fuzzy);
+    Compiler c(idx, dummy, CompileInputs{fuzzy});
     Leaf l;
     l.part = &part;
     l.get_scores = true;
@@ -2628,7 +2622,7 @@ std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPa
     lookup.snippet.reset();
     lookup.has_snippet_info = false;
     Request dummy;
-    Compiler c(idx, dummy, fuzzy);
+    Compiler c(idx, dummy, CompileInputs{fuzzy});
     Leaf l;
     l.part = &lookup;
     l.get_scores = true;
@@ -2912,8 +2906,7 @@ bool request_wants_explain(const vqreq::Request& req) {
     return any;
 }
 
-CompiledQuery compile_query(const Index& idx, const vqreq::Request& req_in, const FuzzyTable* fuzzy, const UnionTable* unions, const QueryCounts* counts,
-                            const RangeTable* ranges, Boost1nCache* boost_cache, const LocalityTable* localities) {
+CompiledQuery compile_query(const Index& idx, const vqreq::Request& req_in, const CompileInputs& in) {
     std::unique_ptr<Request> explained;
     if (req_in.explain) {
         explained = std::make_unique<Request>(req_in);
@@ -2921,12 +2914,7 @@ CompiledQuery compile_query(const Index& idx, const vqreq::Request& req_in, cons
     }
     const vqreq::Request& req = explained ? *explained : req_in;
     PhaseTimer pt(5);
-    Compiler c(idx, req, fuzzy);
-    c.boost_cache = boost_cache;
-    c.localities = localities;
-    c.unions = unions;
-    c.counts = counts;
-    c.ranges = ranges;
+    Compiler c(idx, req, in);
     try {
         c.run();
         if (!c.cq.range_requests.empty()) {

@@ -676,9 +676,17 @@ struct CompiledQuery {
 };
 
 KernelId route_query(const CompiledQuery& cq);
-CompiledQuery compile_query(const Index& idx, const vqreq::Request& req, const FuzzyTable* fuzzy = nullptr, const UnionTable* unions = nullptr,
-                            const QueryCounts* counts = nullptr, const RangeTable* ranges = nullptr, Boost1nCache* boost_cache = nullptr,
-                            const LocalityTable* localities = nullptr);
+// What the pre-passes of a batch have found so far, as one compilation pass sees it.  Null and non-null differ: the compiler asks for a union /
+// range / locality job where it has no table and reads the job's result where it has one (exec.cpp: BatchTables hands these out per pass).
+struct CompileInputs {
+    const FuzzyTable* fuzzy = nullptr;
+    const UnionTable* unions = nullptr;
+    const QueryCounts* counts = nullptr;
+    const RangeTable* ranges = nullptr;
+    Boost1nCache* boost_cache = nullptr;
+    const LocalityTable* localities = nullptr;
+};
+CompiledQuery compile_query(const Index& idx, const vqreq::Request& req, const CompileInputs& in = {});
 void run_locality_jobs(const Index& idx, Workspace& ws, LocalityTable& table, hipStream_t st);
 void run_boost1n_jobs(const Index& idx, Workspace& ws, Boost1nTable& table, hipStream_t st);
 void run_range_jobs(const Index& idx, Workspace& ws, RangeTable& table, const UnionTable& unions, hipStream_t st);

@@ -1117,7 +1117,6 @@ static void run_count_queries(const Index& idx, Workspace& ws, const std::vector
     }
 }
 
-
 // blob and descriptor size of a compiled query (a dry run of pack_blob), kept with it: the serial part of a step does not walk every query three times
 static void size_blob(CompiledQuery& cq, const Index& idx) {
     if (cq.status != 0) return;
@@ -1126,65 +1125,80 @@ static void size_blob(CompiledQuery& cq, const Index& idx) {
     cq.desc_bytes = d;
 }
 
-std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot, int64_t arena_offset) {
-    const double t_start = now_ms();
-    auto pb = std::make_unique<PartialBatch>();
-    pb->index = &idx;
-    pb->reqs.assign(reqs, reqs + n);
-    pb->t0 = std::chrono::steady_clock::now();
+// ---- run_partial: the host side of a step, phase by phase (the functions follow in the order run_partial calls them)
+
+// A workspace for the batch: any free one (slot < 0), or the one the caller named, which then stays pinned until the batch is finished
+static void acquire_workspace(const Index& idx, PartialBatch& pb, int slot) {
     if (slot < 0) {
         // any workspace: the first free one from the round-robin position on, never one that a batch holds by name (the chunks of a sharded step
         // in flight: waiting for one of those on the thread that has to end the step would never return)
         const uint32_t start = idx.next_ws.fetch_add(1);
         int fallback = -1;
-        for (uint32_t k = 0; k < uint32_t(kWorkspaces) && !pb->lock.owns_lock(); ++k) {
+        for (uint32_t k = 0; k < uint32_t(kWorkspaces) && !pb.lock.owns_lock(); ++k) {
             Workspace& w = idx.ws[(start + k) % kWorkspaces];
             if (w.pinned.load(std::memory_order_acquire)) continue;
             if (fallback < 0) fallback = int((start + k) % kWorkspaces);
             std::unique_lock<std::mutex> l(w.mu, std::try_to_lock);
             if (l.owns_lock() && !w.pinned.load(std::memory_order_acquire)) {
-                pb->ws = &w;
-                pb->lock = std::move(l);
+                pb.ws = &w;
+                pb.lock = std::move(l);
             }
         }
-        if (!pb->lock.owns_lock()) {
+        if (!pb.lock.owns_lock()) {
             if (fallback < 0) throw vqreq::VelociError(vqreq::ERR_INVALID_ARGUMENT, "every workspace of the index is held by a sharded step in flight: end a step first");
-            pb->ws = &idx.ws[fallback];  // held by another thread's batch: it will be handed on
-            pb->lock = std::unique_lock<std::mutex>(pb->ws->mu);
+            pb.ws = &idx.ws[fallback];  // held by another thread's batch: it will be handed on
+            pb.lock = std::unique_lock<std::mutex>(pb.ws->mu);
         }
     } else {
-        pb->ws = &idx.ws[slot % kWorkspaces];
-        pb->lock = std::unique_lock<std::mutex>(pb->ws->mu, std::try_to_lock);
-        if (!pb->lock.owns_lock()) {
-            if (pb->ws->pinned.load(std::memory_order_acquire)) throw vqreq::VelociError(vqreq::ERR_INVALID_ARGUMENT, "the workspace named for this batch is held by a step in flight");
-            pb->lock = std::unique_lock<std::mutex>(pb->ws->mu);
+        pb.ws = &idx.ws[slot % kWorkspaces];
+        pb.lock = std::unique_lock<std::mutex>(pb.ws->mu, std::try_to_lock);
+        if (!pb.lock.owns_lock()) {
+            if (pb.ws->pinned.load(std::memory_order_acquire)) throw vqreq::VelociError(vqreq::ERR_INVALID_ARGUMENT, "the workspace named for this batch is held by a step in flight");
+            pb.lock = std::unique_lock<std::mutex>(pb.ws->mu);
         }
-        pb->ws->pinned.store(true, std::memory_order_release);
-        pb->pinned_ws = true;
+        pb.ws->pinned.store(true, std::memory_order_release);
+        pb.pinned_ws = true;
     }
-    VQ_HIP(hipSetDevice(idx.device));
-    Workspace& ws = *pb->ws;
-    hipStream_t st = idx.stream;
-    ws.timed.clear();
-    ws.ev_used = 0;
-    pb->profiled = idx.profile.enabled;
+}
 
-    // ---- dictionary scans (fuzzy / prefix leaves) of the whole batch, then compile
-    FuzzyTable fuzzy;
-    for (size_t i = 0; i < n; ++i)
-        if (reqs[i]) collect_fuzzy_probes(idx, *reqs[i], fuzzy);
-    static const bool pre_own = std::getenv("VQ_PRE_ON_SCAN_STREAM") == nullptr;
-    hipStream_t pst = pre_own && idx.pre_stream ? idx.pre_stream : st;  // the pre-passes' stream (see Index::pre_stream)
-    if (!fuzzy.empty()) run_fuzzy_probes(idx, ws, fuzzy, pst);
-    const double t_probes = now_ms();
-    pb->queries.reserve(n);
-    pb->slot.assign(n, UINT32_MAX);
-    pb->queries.resize(n);
+// What the pre-passes of one batch have produced so far; compile_batch owns it and hands every compilation pass its view
+struct BatchTables {
+    FuzzyTable fuzzy;          // dictionary scans of the fuzzy / prefix / regex leaves
+    UnionTable unions;         // K2
+    RangeTable ranges;
+    LocalityTable localities;  // K7
+    Boost1nTable boost1n;      // K10 (the compiler reaches it through boost_cache.device)
     Boost1nCache boost_cache;  // resolved 1:n boost lists, shared by the batch's requests and compilation passes
+    // Pass 1 sees the dictionary scans and the 1:n cache and none of the job tables, whatever they hold: without a table a leaf ASKS for its job
+    CompileInputs first_pass() {
+        CompileInputs in;
+        in.fuzzy = fuzzy.empty() ? nullptr : &fuzzy;
+        in.boost_cache = &boost_cache;
+        return in;
+    }
+    // Every later pass sees all of them, an empty table as null; the final pass also the count pre-pass's numbers for its query
+    CompileInputs later_pass(const QueryCounts* counts = nullptr) {
+        CompileInputs in = first_pass();
+        in.unions = unions.empty() ? nullptr : &unions;
+        in.ranges = ranges.empty() ? nullptr : &ranges;
+        in.localities = localities.empty() ? nullptr : &localities;
+        in.counts = counts;
+        return in;
+    }
+};
+struct CompileReport {  // what report_timing quotes of compile_batch
+    double t_probes = 0, t_pass1 = 0, t_unions = 0, t_ranges = 0, t_compiled = 0;
+    size_t probes = 0, unions = 0, ranges = 0;
+};
+
+// Pass 1: every request compiled once, from 64 requests on over the index's host threads.  Leaves `order`, the order the requests were taken in,
+// and returns whether that was heaviest first.
+static bool compile_first_pass(const Index& idx, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, BatchTables& tables, std::vector<uint32_t>& order) {
     // Requests are compiled heaviest first: a request's cost follows the terms its prefix / fuzzy leaves matched (their posting lists, the 1:n boost
     // lists behind them), which the dictionary scans have just counted; one such request can take as long as a hundred others, and claimed last
     // it alone would be the end of the parallel pass.
-    std::vector<uint32_t> order(n);
+    const FuzzyTable& fuzzy = tables.fuzzy;
+    order.resize(n);
     for (size_t i = 0; i < n; ++i) order[i] = uint32_t(i);
     const bool heavy_first = n >= 64 && !fuzzy.empty() && host_threads() > 1;
     if (heavy_first) {
@@ -1201,15 +1215,16 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
             if (reqs[i] && reqs[i]->search_req) walk(*reqs[i]->search_req, weight[i]);
         std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return weight[x] > weight[y]; });
     }
+    const CompileInputs in = tables.first_pass();
     auto compile_range = [&](size_t b, size_t e) {
         for (size_t k = b; k < e; ++k) {
             const size_t i = order[k];
             if (!reqs[i]) {
-                pb->queries[i].status = ERR_INVALID_ARGUMENT;
-                pb->queries[i].error = "null request";
+                pb.queries[i].status = ERR_INVALID_ARGUMENT;
+                pb.queries[i].error = "null request";
             } else {
-                pb->queries[i] = compile_query(idx, *reqs[i], fuzzy.empty() ? nullptr : &fuzzy, nullptr, nullptr, nullptr, &boost_cache);
-                size_blob(pb->queries[i], idx);
+                pb.queries[i] = compile_query(idx, *reqs[i], in);
+                size_blob(pb.queries[i], idx);
             }
         }
     };
@@ -1218,257 +1233,263 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
         // one request): few claims while everybody is busy, single requests at the end — a worker that wakes late (an idle core takes ~0.1 ms,
         // a third of the whole job) still finds work, and requests of very different cost (a prefix leaf with a 1:n boost list takes 1000x a
         // plain AND) balance out.
-        const std::vector<std::pair<size_t, size_t>> ranges = guided_ranges(n, host_threads(), heavy_first ? 4 * host_threads() : 0);
-        host_pool(idx).run(ranges.size(), [&](size_t p) { compile_range(ranges[p].first, ranges[p].second); });
+        const std::vector<std::pair<size_t, size_t>> parts = guided_ranges(n, host_threads(), heavy_first ? 4 * host_threads() : 0);
+        host_pool(idx).run(parts.size(), [&](size_t p) { compile_range(parts[p].first, parts[p].second); });
     } else compile_range(0, n);
-    const double t_pass1 = now_ms();
+    return heavy_first;
+}
+
+// Leaves that asked to be materialised first (K2): the union, locality and 1:n-boost jobs run once per batch, then the requests that asked are
+// compiled again with the results — up to twice, around the range jobs
+static void compile_with_jobs(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, const std::vector<uint32_t>& order, bool heavy_first,
+                              BatchTables& tables, hipStream_t pst, CompileReport& rep) {
+    std::vector<size_t> again;
+    for (size_t k = 0; k < order.size(); ++k)
+        if (const size_t i = order[k]; pb.queries[i].status == kStatusNeedsUnion || pb.queries[i].status == kStatusNeedsRanges) {
+            again.push_back(i);
+            for (auto& j : pb.queries[i].union_requests) tables.unions.emplace(j.key, j);
+            for (auto& j : pb.queries[i].locality_requests) tables.localities.emplace(j.key, j);
+            for (auto& j : pb.queries[i].boost1n_requests) tables.boost1n.emplace(j.key, j);
+        }
+    if (again.empty()) return;
+    if (!tables.unions.empty()) {
+        run_union_jobs(idx, ws, tables.unions, pst);
+        // merged lengths over all shards (the AND summation order follows them)
+        std::vector<uint64_t> lens;
+        for (auto& kv : tables.unions) lens.push_back(kv.second.len);
+        if (idx.can_sum_over_shards()) idx.sum_over_shards(lens);
+        size_t k = 0;
+        for (auto& kv : tables.unions) kv.second.global_len = lens[k++];
+    }
+    if (!tables.localities.empty()) run_locality_jobs(idx, ws, tables.localities, pst);
+    if (!tables.boost1n.empty()) {
+        run_boost1n_jobs(idx, ws, tables.boost1n, pst);
+        tables.boost_cache.device = &tables.boost1n;
+    }
+    rep.t_unions = rep.t_ranges = now_ms();
+    // Compile again with the jobs' results.  A 1:n boost list only shows once it is resolved (K10) whether an anchor carries several values:
+    // those leaves then ask for a range pre-pass — which of the values apply follows the leaf's hits around each anchor (k_range_hits, on the
+    // merged list of a materialised leaf) — and are compiled a third time.
+    for (int round = 0; round < 2 && !again.empty(); ++round) {
+        bool any_ranges = false;
+        for (size_t i : again)
+            if (pb.queries[i].status == kStatusNeedsRanges) {
+                any_ranges = true;
+                for (auto& j : pb.queries[i].range_requests) tables.ranges.emplace(j.key, j);
+            }
+        const bool ranges_ok = !any_ranges || !idx.sharded() || idx.can_sum_over_shards();
+        if (any_ranges && ranges_ok) run_range_jobs(idx, ws, tables.ranges, tables.unions, pst);
+        rep.t_ranges = now_ms();
+        const CompileInputs in = tables.later_pass();
+        auto recompile = [&](size_t b, size_t e) {
+            for (size_t k = b; k < e; ++k) {
+                CompiledQuery& q = pb.queries[again[k]];
+                if (q.status == kStatusNeedsRanges && !ranges_ok) {
+                    q.status = ERR_UNSUPPORTED;
+                    q.error = "unsupported on the MI355X query path: 1:n field boost with several boosted values on one anchor, on a sharded index without vq_index_set_allreduce";
+                    continue;
+                }
+                q = compile_query(idx, *reqs[again[k]], in);
+                if (q.status == kStatusNeedsUnion || (q.status == kStatusNeedsRanges && round == 1)) {
+                    q.status = ERR_UNSUPPORTED;
+                    q.error = "unsupported on the MI355X query path: leaf expansion changed between compilation passes (internal)";
+                }
+                size_blob(q, idx);
+            }
+        };
+        if (again.size() >= 8 && host_threads() > 1) {
+            const std::vector<std::pair<size_t, size_t>> parts = guided_ranges(again.size(), host_threads(), heavy_first ? 4 * host_threads() : 0);
+            host_pool(idx).run(parts.size(), [&](size_t p) { recompile(parts[p].first, parts[p].second); });
+        } else recompile(0, again.size());
+        std::vector<size_t> still;
+        for (size_t i : again)
+            if (pb.queries[i].status == kStatusNeedsRanges) still.push_back(i);
+        again.swap(still);
+    }
+}
+
+// ANDs whose summation order / label follow run-time operand sizes: count pre-pass, then the final compilation
+static void compile_with_counts(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, BatchTables& tables, hipStream_t pst) {
+    std::vector<size_t> need;
+    std::vector<CompiledQuery*> cqs;
+    for (size_t i = 0; i < pb.queries.size(); ++i)
+        if (pb.queries[i].status == kStatusNeedsCounts) {
+            need.push_back(i);
+            cqs.push_back(&pb.queries[i]);
+        }
+    if (need.empty()) return;
+    std::vector<QueryCounts> counts;
+    run_count_queries(idx, ws, cqs, counts, pst);
+    if (idx.sharded()) {  // result sizes are sums over the shards
+        auto each = [&](auto&& f) {  // every number of the counts, in one order
+            for (auto& c : counts) {
+                f(c.filter_count);
+                for (auto& kv : c.nodes) f(kv.second.first), f(kv.second.second);
+            }
+        };
+        std::vector<uint64_t> flat;
+        each([&](uint64_t& v) { flat.push_back(v); });
+        idx.sum_over_shards(flat);
+        size_t k = 0;
+        each([&](uint64_t& v) { v = flat[k++]; });
+    }
+    for (size_t k = 0; k < need.size(); ++k) {
+        CompiledQuery& q = pb.queries[need[k]];
+        q = compile_query(idx, *reqs[need[k]], tables.later_pass(&counts[k]));
+        if (q.status < 0) {
+            q.status = ERR_UNSUPPORTED;
+            q.error = "unsupported on the MI355X query path: query still needs a pre-pass after the count pre-pass (internal)";
+        }
+    }
+}
+
+// Dictionary scans (fuzzy / prefix leaves) of the whole batch, then its compilation passes with the pre-passes between them: pb.queries
+static CompileReport compile_batch(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, hipStream_t st) {
+    CompileReport rep;
+    BatchTables tables;
+    for (size_t i = 0; i < n; ++i)
+        if (reqs[i]) collect_fuzzy_probes(idx, *reqs[i], tables.fuzzy);
+    static const bool pre_own = std::getenv("VQ_PRE_ON_SCAN_STREAM") == nullptr;
+    hipStream_t pst = pre_own && idx.pre_stream ? idx.pre_stream : st;  // the pre-passes' stream (see Index::pre_stream)
+    if (!tables.fuzzy.empty()) run_fuzzy_probes(idx, ws, tables.fuzzy, pst);
+    rep.t_probes = now_ms();
+    pb.queries.reserve(n);
+    pb.slot.assign(n, UINT32_MAX);
+    pb.queries.resize(n);
+    std::vector<uint32_t> order;
+    const bool heavy_first = compile_first_pass(idx, pb, reqs, n, tables, order);
+    rep.t_pass1 = rep.t_unions = rep.t_ranges = now_ms();
     if (timing_enabled() && std::getenv("VQ_TIMING_SUB")) {  // (tools/host_profile.py stops at the first launch: the running totals, pass 1 only)
-        std::fprintf(stderr, "[vq timing] pass 1 of %zu: %.3f ms wall;", n, t_pass1 - t_probes);
+        std::fprintf(stderr, "[vq timing] pass 1 of %zu: %.3f ms wall;", n, rep.t_pass1 - rep.t_probes);
         for (int k = 0; k < 10; ++k) std::fprintf(stderr, " [%d] %.3f", k, g_compile_ns[k].load() * 1e-6);
         std::fprintf(stderr, "\n");
     }
-    // ---- leaves that asked to be materialised first (K2): run the union jobs once per batch
-    UnionTable unions;
-    RangeTable ranges;
-    LocalityTable localities;
-    Boost1nTable boost1n;
-    std::vector<size_t> again;
-    for (size_t k = 0; k < n; ++k)
-        if (const size_t i = order[k]; pb->queries[i].status == kStatusNeedsUnion || pb->queries[i].status == kStatusNeedsRanges) {
-            again.push_back(i);
-            for (auto& j : pb->queries[i].union_requests) unions.emplace(j.key, j);
-            for (auto& j : pb->queries[i].locality_requests) localities.emplace(j.key, j);
-            for (auto& j : pb->queries[i].boost1n_requests) boost1n.emplace(j.key, j);
-        }
-    double t_unions = t_pass1, t_ranges = t_pass1;
-    if (!again.empty()) {
-        if (!unions.empty()) {
-            run_union_jobs(idx, ws, unions, pst);
-            // merged lengths over all shards (the AND summation order follows them)
-            std::vector<uint64_t> lens;
-            for (auto& kv : unions) lens.push_back(kv.second.len);
-            if (idx.can_sum_over_shards()) idx.sum_over_shards(lens);
-            size_t k = 0;
-            for (auto& kv : unions) kv.second.global_len = lens[k++];
-        }
-        if (!localities.empty()) run_locality_jobs(idx, ws, localities, pst);
-        if (!boost1n.empty()) {
-            run_boost1n_jobs(idx, ws, boost1n, pst);
-            boost_cache.device = &boost1n;
-        }
-        t_unions = t_ranges = now_ms();
-        // Compile again with the jobs' results.  A 1:n boost list only shows once it is resolved (K10) whether an anchor carries several values:
-        // those leaves then ask for a range pre-pass — which of the values apply follows the leaf's hits around each anchor (k_range_hits, on the
-        // merged list of a materialised leaf) — and are compiled a third time.
-        for (int round = 0; round < 2 && !again.empty(); ++round) {
-            bool any_ranges = false;
-            for (size_t i : again)
-                if (pb->queries[i].status == kStatusNeedsRanges) {
-                    any_ranges = true;
-                    for (auto& j : pb->queries[i].range_requests) ranges.emplace(j.key, j);
-                }
-            const bool ranges_ok = !any_ranges || !idx.sharded() || idx.can_sum_over_shards();
-            if (any_ranges && ranges_ok) run_range_jobs(idx, ws, ranges, unions, pst);
-            t_ranges = now_ms();
-            auto recompile = [&](size_t b, size_t e) {
-                for (size_t k = b; k < e; ++k) {
-                    CompiledQuery& q = pb->queries[again[k]];
-                    if (q.status == kStatusNeedsRanges && !ranges_ok) {
-                        q.status = ERR_UNSUPPORTED;
-                        q.error = "unsupported on the MI355X query path: 1:n field boost with several boosted values on one anchor, on a sharded index without vq_index_set_allreduce";
-                        continue;
-                    }
-                    q = compile_query(idx, *reqs[again[k]], fuzzy.empty() ? nullptr : &fuzzy, unions.empty() ? nullptr : &unions, nullptr, ranges.empty() ? nullptr : &ranges, &boost_cache,
-                                      localities.empty() ? nullptr : &localities);
-                    if (q.status == kStatusNeedsUnion || (q.status == kStatusNeedsRanges && round == 1)) {
-                        q.status = ERR_UNSUPPORTED;
-                        q.error = "unsupported on the MI355X query path: leaf expansion changed between compilation passes (internal)";
-                    }
-                    size_blob(q, idx);
-                }
-            };
-            if (again.size() >= 8 && host_threads() > 1) {
-                const std::vector<std::pair<size_t, size_t>> ranges = guided_ranges(again.size(), host_threads(), heavy_first ? 4 * host_threads() : 0);
-                host_pool(idx).run(ranges.size(), [&](size_t p) { recompile(ranges[p].first, ranges[p].second); });
-            } else recompile(0, again.size());
-            std::vector<size_t> still;
-            for (size_t i : again)
-                if (pb->queries[i].status == kStatusNeedsRanges) still.push_back(i);
-            again.swap(still);
+    compile_with_jobs(idx, ws, pb, reqs, order, heavy_first, tables, pst, rep);
+    compile_with_counts(idx, ws, pb, reqs, tables, pst);
+    rep.t_compiled = now_ms();
+    rep.probes = tables.fuzzy.size(), rep.unions = tables.unions.size(), rep.ranges = tables.ranges.size();
+    return rep;
+}
+
+// Spans per query: a small batch is split further, and requests of very different weight get spans in proportion to their postings
+static void size_spans(std::vector<CompiledQuery>& queries) {
+    const size_t n = queries.size();
+    // a small batch (one query = the latency case) would leave most of the chip idle with spans sized for streaming efficiency:
+    // split its queries further until the launch holds about one wave per SIMD of every CU
+    static const uint64_t target1 = [] {
+        const char* e = std::getenv("VQ_SPAN_TARGET");
+        return uint64_t(e ? std::atoll(e) : 2048);
+    }();
+    // (one request: 2048 spans — its merge is serial in the span count; more requests merge in parallel: up to one wave per slot)
+    const uint64_t target = std::min<uint64_t>(target1 + 64 * uint64_t(n - 1), std::max<uint64_t>(target1, 5120));
+    uint64_t have = 0, total_postings = 0;
+    for (const CompiledQuery& cq : queries)
+        if (cq.status == 0) have += cq.n_spans, total_postings += cq.total_len;
+    if (have && have * 3 <= target * 2) {
+        const uint64_t f = (target + have - 1) / have;
+        for (CompiledQuery& cq : queries)
+            if (cq.status == 0) cq.n_spans = uint32_t(std::max<uint64_t>(cq.n_spans, std::min<uint64_t>(uint64_t(cq.n_spans) * f, cq.max_spans)));
+    }
+    // Requests of very different weight in one launch (a prefix leaf over a third of the documents beside exact matches of a few): the launch
+    // ends with the longest span, so a request gets spans in proportion to its postings — as many as keep every span of the launch near
+    // total / target postings, but no span below 4096 (bench_jmdict shape, 256 requests: k_tile_scan 4.1 -> 0.8 ms)
+    static const bool weighted = std::getenv("VQ_NO_WEIGHTED_SPANS") == nullptr;
+    if (weighted && n > 1 && total_postings) {
+        const uint64_t per_span = std::max<uint64_t>(total_postings / target, 4096);
+        for (CompiledQuery& cq : queries) {
+            if (cq.status != 0) continue;
+            const uint64_t want = std::min<uint64_t>((cq.total_len + per_span - 1) / per_span, cq.max_spans);
+            cq.n_spans = uint32_t(std::max<uint64_t>(cq.n_spans, want));
         }
     }
-    const RangeTable* rangesp = ranges.empty() ? nullptr : &ranges;
-    // ---- ANDs whose summation order / label follow run-time operand sizes: count pre-pass, then the final compilation
-    {
-        std::vector<size_t> need;
-        std::vector<CompiledQuery*> cqs;
-        for (size_t i = 0; i < n; ++i)
-            if (pb->queries[i].status == kStatusNeedsCounts) {
-                need.push_back(i);
-                cqs.push_back(&pb->queries[i]);
-            }
-        if (!need.empty()) {
-            std::vector<QueryCounts> counts;
-            run_count_queries(idx, ws, cqs, counts, pst);
-            if (idx.sharded()) {  // result sizes are sums over the shards
-                std::vector<uint64_t> flat;
-                for (auto& c : counts) {
-                    flat.push_back(c.filter_count);
-                    for (auto& kv : c.nodes) {
-                        flat.push_back(kv.second.first);
-                        flat.push_back(kv.second.second);
-                    }
-                }
-                idx.sum_over_shards(flat);
-                size_t k = 0;
-                for (auto& c : counts) {
-                    c.filter_count = flat[k++];
-                    for (auto& kv : c.nodes) {
-                        kv.second.first = flat[k++];
-                        kv.second.second = flat[k++];
-                    }
-                }
-            }
-            for (size_t k = 0; k < need.size(); ++k) {
-                CompiledQuery& q = pb->queries[need[k]];
-                q = compile_query(idx, *reqs[need[k]], fuzzy.empty() ? nullptr : &fuzzy, unions.empty() ? nullptr : &unions, &counts[k], rangesp, &boost_cache,
-                                  localities.empty() ? nullptr : &localities);
-                if (q.status < 0) {
-                    q.status = ERR_UNSUPPORTED;
-                    q.error = "unsupported on the MI355X query path: query still needs a pre-pass after the count pre-pass (internal)";
-                }
-            }
-        }
-    }
-    const double t_compiled = now_ms();
-    // ---- layout
+}
+
+// Where the batch's device queries lie, per slot: span keys, part of the partial, facet histograms and outputs; the totals the launches are sized by
+struct BatchLayout {
     uint32_t nq = 0;
     uint64_t total_keys = 0, total_hist = 0, total_span_keys = 0, total_spans = 0, blob_bytes = 0;
-    uint32_t max_lists = 1, max_ww = 32;
-    size_t lds_bytes = 0;
-    uint32_t stack_depth = 1;
-    std::vector<uint32_t> keys_base, part_keys_off, span_base;
+    uint32_t max_lists = 1, stack_depth = 1;
+    std::vector<uint32_t> keys_base, part_keys_off;
     std::vector<std::vector<uint32_t>> hist_offs, fac_out_offs;
+};
+// Slots of the queries that compiled, their offsets, the facet jobs, pb.layout
+static BatchLayout plan_layout(const Index& idx, PartialBatch& pb) {
+    BatchLayout L;
     std::vector<FacetJob> jobs;
     uint32_t fac_out_total = 0;
-    {   // a small batch (one query = the latency case) would leave most of the chip idle with spans sized for streaming efficiency:
-        // split its queries further until the launch holds about one wave per SIMD of every CU
-        static const uint64_t target1 = [] {
-            const char* e = std::getenv("VQ_SPAN_TARGET");
-            return uint64_t(e ? std::atoll(e) : 2048);
-        }();
-        // (one request: 2048 spans — its merge is serial in the span count; more requests merge in parallel: up to one wave per slot)
-        const uint64_t target = std::min<uint64_t>(target1 + 64 * uint64_t(n - 1), std::max<uint64_t>(target1, 5120));
-        uint64_t have = 0;
-        for (size_t i = 0; i < n; ++i)
-            if (pb->queries[i].status == 0) have += pb->queries[i].n_spans;
-        if (have && have * 3 <= target * 2) {
-            const uint64_t f = (target + have - 1) / have;
-            for (size_t i = 0; i < n; ++i) {
-                CompiledQuery& cq = pb->queries[i];
-                if (cq.status == 0) cq.n_spans = uint32_t(std::max<uint64_t>(cq.n_spans, std::min<uint64_t>(uint64_t(cq.n_spans) * f, cq.max_spans)));
-            }
-        }
-        // Requests of very different weight in one launch (a prefix leaf over a third of the documents beside exact matches of a few): the launch
-        // ends with the longest span, so a request gets spans in proportion to its postings — as many as keep every span of the launch near
-        // total / target postings, but no span below 4096 (bench_jmdict shape, 256 requests: k_tile_scan 4.1 -> 0.8 ms)
-        static const bool weighted = std::getenv("VQ_NO_WEIGHTED_SPANS") == nullptr;
-        uint64_t total_postings = 0;
-        for (size_t i = 0; i < n; ++i)
-            if (pb->queries[i].status == 0) total_postings += pb->queries[i].total_len;
-        if (weighted && n > 1 && total_postings) {
-            const uint64_t per_span = std::max<uint64_t>(total_postings / target, 4096);
-            for (size_t i = 0; i < n; ++i) {
-                CompiledQuery& cq = pb->queries[i];
-                if (cq.status != 0) continue;
-                const uint64_t want = std::min<uint64_t>((cq.total_len + per_span - 1) / per_span, cq.max_spans);
-                cq.n_spans = uint32_t(std::max<uint64_t>(cq.n_spans, want));
-            }
-        }
-    }
-    for (size_t i = 0; i < n; ++i) {
-        CompiledQuery& cq = pb->queries[i];
+    for (size_t i = 0; i < pb.queries.size(); ++i) {
+        CompiledQuery& cq = pb.queries[i];
         if (cq.status != 0) continue;
-        pb->slot[i] = nq++;
-        keys_base.push_back(uint32_t(total_span_keys));
-        part_keys_off.push_back(uint32_t(total_keys));
-        span_base.push_back(uint32_t(total_spans));
-        total_span_keys += uint64_t(cq.n_spans) * cq.top_k;
-        total_keys += cq.top_k;
-        total_spans += cq.n_spans;
+        pb.slot[i] = L.nq++;
+        L.keys_base.push_back(uint32_t(L.total_span_keys));
+        L.part_keys_off.push_back(uint32_t(L.total_keys));
+        L.total_span_keys += uint64_t(cq.n_spans) * cq.top_k;
+        L.total_keys += cq.top_k;
+        L.total_spans += cq.n_spans;
         std::vector<uint32_t> ho, fo;
         for (auto& f : cq.facets) {
-            ho.push_back(uint32_t(total_hist));
+            ho.push_back(uint32_t(L.total_hist));
             fo.push_back(fac_out_total);
-            jobs.push_back(FacetJob{uint32_t(total_hist), f.num_values, f.top, fac_out_total});
-            total_hist += f.num_values;
+            jobs.push_back(FacetJob{uint32_t(L.total_hist), f.num_values, f.top, fac_out_total});
+            L.total_hist += f.num_values;
             fac_out_total += f.top;
         }
-        hist_offs.push_back(std::move(ho));
-        fac_out_offs.push_back(std::move(fo));
+        L.hist_offs.push_back(std::move(ho));
+        L.fac_out_offs.push_back(std::move(fo));
         if (!cq.blob_bytes) size_blob(cq, idx);  // (normally taken on the compiling thread)
-        blob_bytes += cq.blob_bytes;
-        max_lists = std::max<uint32_t>(max_lists, uint32_t(cq.lists.size()));
-        max_ww = std::max(max_ww, cq.tile_words);
-        stack_depth = std::max(stack_depth, cq.stack_depth);
+        L.blob_bytes += cq.blob_bytes;
+        L.max_lists = std::max<uint32_t>(L.max_lists, uint32_t(cq.lists.size()));
+        L.stack_depth = std::max(L.stack_depth, cq.stack_depth);
     }
-    if (total_span_keys > 0xFFFFFFFFull || total_hist > 0xFFFFFFFFull || total_spans > 0x7FFFFFFFull)
+    if (L.total_span_keys > 0xFFFFFFFFull || L.total_hist > 0xFFFFFFFFull || L.total_spans > 0x7FFFFFFFull)
         throw VelociError(ERR_UNSUPPORTED, "batch too large for 32-bit workspace offsets: split the batch");
-    span_base.push_back(uint32_t(total_spans));
-    pb->nq_dev = nq;
-    pb->total_spans = uint32_t(total_spans);
-    pb->n_facet_jobs = uint32_t(jobs.size());
-    pb->total_facet_out = fac_out_total;
-    pb->facet_jobs = jobs;
-    const double t_layout = now_ms();
+    pb.nq_dev = L.nq;
+    pb.total_spans = uint32_t(L.total_spans);
+    pb.n_facet_jobs = uint32_t(jobs.size());
+    pb.total_facet_out = fac_out_total;
+    pb.facet_jobs = std::move(jobs);
 
-    PartialLayout& lay = pb->layout;
-    lay.nq = nq;
-    lay.total_keys = total_keys;
-    lay.total_hist = total_hist;
+    PartialLayout& lay = pb.layout;
+    lay.nq = L.nq;
+    lay.total_keys = L.total_keys;
+    lay.total_hist = L.total_hist;
     lay.off_hits = 0;
-    lay.off_stats = align_up(size_t(nq) * 8, 16);
-    lay.off_keys = lay.off_stats + align_up(size_t(nq) * 8, 16);
-    lay.off_hist = align_up(lay.off_keys + size_t(total_keys) * 8, 256);  // == bytes of the all-gathered part
-    lay.bytes = align_up(lay.off_hist + size_t(total_hist) * 4, 256);
+    lay.off_stats = align_up(size_t(L.nq) * 8, 16);
+    lay.off_keys = lay.off_stats + align_up(size_t(L.nq) * 8, 16);
+    lay.off_hist = align_up(lay.off_keys + size_t(L.total_keys) * 8, 256);  // == bytes of the all-gathered part
+    lay.bytes = align_up(lay.off_hist + size_t(L.total_hist) * 4, 256);
+    return L;
+}
 
-    // ---- upload area: [blobs][blob_off][span tables][qmap tables][facet jobs]
-    // One (span_base, qmap) table per scan launch, in launch order: span_base = prefix sums of n_spans over the launch's queries (and a closing
-    // entry), qmap = the blob slot of its k-th query.  The tables lie one behind the other, each as long as its launch has queries.
-    enum : uint32_t { T_LEAF_F32 = 0, T_RICH, T_PROBE, T_AND = T_PROBE + kProbeShapes, T_SIMPLE, T_UNION, T_WIDE, T_TILE, kScanTables };
-    struct ScanTable {
-        uint32_t first = 0;                       // of its entries inside the span / qmap areas
-        uint32_t *span_base = nullptr, *qmap = nullptr;  // host side of the upload area
-        uint32_t n = 0, spans = 0;                // queries, spans
-    } tabs[kScanTables];
-    auto table_of = [](const CompiledQuery& cq) -> uint32_t {
-        switch (cq.kclass) {
-            case K_SCAN_LEAF_F32: return T_LEAF_F32;
-            case K_SCAN_RICH: return T_RICH;
-            case K_SCAN_PROBE: {  // a kernel per shape: OR / AND of ND operands beside the cover, from ND = 2 on per number of array operands
-                if (sf_probe_or(cq.simple_flags)) return T_PROBE + kProbeOr;
-                const uint32_t nd = cq.simple_n - 1, na = uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
-                return T_PROBE + (nd <= 1 ? kProbeAnd1 : nd == 2 ? kProbeAnd2A0 + na : kProbeAnd3A0 + na);
-            }
-            case K_SCAN_AND: return T_AND;
-            case K_SCAN_SIMPLE: return T_SIMPLE;
-            case K_SCAN_UNION: return T_UNION;
-            case K_SCAN_WIDE: return T_WIDE;
-            case K_TILE_SCAN: return T_TILE;
-            default: throw VelociError(ERR_DEVICE, "query without a scan class (internal)");
+// One (span_base, qmap) table per scan launch, in launch order: span_base = prefix sums of n_spans over the launch's queries (and a closing
+// entry), qmap = the blob slot of its k-th query.  The tables lie one behind the other, each as long as its launch has queries.
+enum : uint32_t { T_LEAF_F32 = 0, T_RICH, T_PROBE, T_AND = T_PROBE + kProbeShapes, T_SIMPLE, T_UNION, T_WIDE, T_TILE, kScanTables };
+struct ScanTable {
+    uint32_t *span_base = nullptr, *qmap = nullptr;             // host side of the upload area
+    const uint32_t *d_span_base = nullptr, *d_qmap = nullptr;  // ... and where the launch finds them
+    uint32_t n = 0, spans = 0;                       // queries, spans
+};
+static uint32_t table_of(const CompiledQuery& cq) {
+    switch (cq.kclass) {
+        case K_SCAN_LEAF_F32: return T_LEAF_F32;
+        case K_SCAN_RICH: return T_RICH;
+        case K_SCAN_PROBE: {  // a kernel per shape: OR / AND of ND operands beside the cover, from ND = 2 on per number of array operands
+            if (sf_probe_or(cq.simple_flags)) return T_PROBE + kProbeOr;
+            const uint32_t nd = cq.simple_n - 1, na = uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
+            return T_PROBE + (nd <= 1 ? kProbeAnd1 : nd == 2 ? kProbeAnd2A0 + na : kProbeAnd3A0 + na);
         }
-    };
-    const size_t up_blob_off = align_up(blob_bytes, 256);
-    const size_t tbl = align_up(size_t(nq + kScanTables) * 4, 256);
-    const size_t up_span = up_blob_off + align_up(size_t(nq + 1) * 4, 256);
-    const size_t up_qmap = up_span + tbl;
-    const size_t up_jobs = up_qmap + tbl;
-    const size_t up_bytes = up_jobs + align_up(jobs.size() * sizeof(FacetJob), 256) + 256;
-    ws.h_up.ensure(up_bytes);
-    ws.d_up.ensure(up_bytes);
-    uint8_t* hup = ws.h_up.as<uint8_t>();
-    uint8_t* dup = ws.d_up.as<uint8_t>();
-    // launch parameters, collected over each class's queries
+        case K_SCAN_AND: return T_AND;
+        case K_SCAN_SIMPLE: return T_SIMPLE;
+        case K_SCAN_UNION: return T_UNION;
+        case K_SCAN_WIDE: return T_WIDE;
+        case K_TILE_SCAN: return T_TILE;
+        default: throw VelociError(ERR_DEVICE, "query without a scan class (internal)");
+    }
+}
+// The scan tables inside the upload area [blobs][blob_off][span tables][qmap tables][facet jobs] and each class's launch parameters
+struct ScanPlan {
+    ScanTable tabs[kScanTables];
+    size_t up_bytes = 0;  // of the upload area
     bool union_has_or = false, facets_rich = false;
     uint32_t scatter_and = 0, scatter_simple = 0, scatter_rich = 0;  // id (scattered) lists per query: they alone need an LDS tile in k_scan_simple
     uint32_t leaves_wide = 0, scatter_wide = 0;
@@ -1477,103 +1498,120 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     } probe[kProbeShapes];
     bool any_probe = false;
     uint64_t cls_layout[K_COUNT_] = {}, cls_algo[K_COUNT_] = {}, cls_q[K_COUNT_] = {};
-    {
-        size_t off = 0;
-        uint32_t* hbo = reinterpret_cast<uint32_t*>(hup + up_blob_off);
-        uint32_t qi = 0;
-        for (size_t i = 0; i < n; ++i) {
-            CompiledQuery& cq = pb->queries[i];
-            if (cq.status != 0) continue;
-            hbo[qi] = uint32_t(off);
-            const size_t packed = pack_blob(cq, idx, hup + off, dup + off, keys_base[qi], part_keys_off[qi], hist_offs[qi], fac_out_offs[qi], nullptr,
-                                            pb->profiled ? uint32_t((lay.off_stats - lay.off_hits) / 8 + qi) : 0u);  // 0: the kernels count nothing
-            if (packed != cq.blob_bytes) throw VelociError(ERR_DEVICE, "query blob changed size between compilation and packing (internal)");
-            off += packed;
-            ++qi;
-            ++tabs[table_of(cq)].n;  // pass 1: how many queries every table holds
-        }
-        hbo[nq] = uint32_t(off);
-        uint32_t at = 0;
-        for (ScanTable& t : tabs) {  // ... which places them
-            t.first = at;
-            t.span_base = reinterpret_cast<uint32_t*>(hup + up_span) + at;
-            t.qmap = reinterpret_cast<uint32_t*>(hup + up_qmap) + at;
-            at += t.n + 1;
-            t.n = 0;
-        }
-        qi = 0;
-        for (size_t i = 0; i < n; ++i) {  // pass 2: the tables' entries and the launch parameters
-            const CompiledQuery& cq = pb->queries[i];
-            if (cq.status != 0) continue;
-            const uint32_t ti = table_of(cq);
-            ScanTable& t = tabs[ti];
-            t.span_base[t.n] = t.spans;
-            t.qmap[t.n++] = qi;
-            t.spans += cq.n_spans;
-            const uint32_t n_scatter = cq.simple_n - uint32_t(__builtin_popcount(sf_bitmap_mask(cq.simple_flags)));
-            switch (cq.kclass) {
-                case K_SCAN_WIDE:
-                    leaves_wide = std::max<uint32_t>(leaves_wide, cq.wide.n_leaves);
-                    scatter_wide = std::max<uint32_t>(scatter_wide, cq.wide.n_leaves - uint32_t(__builtin_popcount(cq.wide.bitmap_mask)));
-                    break;
-                case K_SCAN_RICH:
-                    facets_rich = facets_rich || !cq.facets.empty();
-                    scatter_rich = std::max<uint32_t>(scatter_rich, n_scatter + cq.simple2.n_side);
-                    break;
-                case K_SCAN_UNION: union_has_or = union_has_or || cq.simple_n > 1; break;
-                case K_SCAN_PROBE: {
-                    ProbeParams& pp = probe[ti - T_PROBE];
-                    pp.na_seen |= 1u << uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
-                    pp.arr_slot = std::max(pp.arr_slot, cq.probe_arr_gran * 4u);
-                    any_probe = true;
-                    break;
-                }
-                case K_SCAN_AND: scatter_and = std::max(scatter_and, n_scatter); break;
-                case K_SCAN_SIMPLE: scatter_simple = std::max(scatter_simple, n_scatter); break;
-                default: break;
-            }
-            pb->qclass.push_back(uint8_t(cq.kclass));
-            cls_layout[cq.kclass] += cq.layout_bytes;
-            cls_algo[cq.kclass] += cq.algorithmic_bytes;
-            cls_q[cq.kclass] += 1;
-            ++qi;
-        }
-        for (ScanTable& t : tabs) t.span_base[t.n] = t.spans;
-        if (!jobs.empty()) std::memcpy(hup + up_jobs, jobs.data(), jobs.size() * sizeof(FacetJob));
+};
+// Packs the blobs and fills the scan tables in the workspace's pinned upload buffer; sets the batch's device addresses inside the upload area
+static ScanPlan pack_upload(const Index& idx, PartialBatch& pb, const BatchLayout& L) {
+    ScanPlan P;
+    Workspace& ws = *pb.ws;
+    const PartialLayout& lay = pb.layout;
+    const uint32_t nq = L.nq;
+    const size_t up_blob_off = align_up(L.blob_bytes, 256);
+    const size_t tbl = align_up(size_t(nq + kScanTables) * 4, 256);
+    const size_t up_span = up_blob_off + align_up(size_t(nq + 1) * 4, 256);
+    const size_t up_qmap = up_span + tbl;
+    const size_t up_jobs = up_qmap + tbl;
+    P.up_bytes = up_jobs + align_up(pb.facet_jobs.size() * sizeof(FacetJob), 256) + 256;
+    ws.h_up.ensure(P.up_bytes);
+    ws.d_up.ensure(P.up_bytes);
+    uint8_t* hup = ws.h_up.as<uint8_t>();
+    uint8_t* dup = ws.d_up.as<uint8_t>();
+    size_t off = 0;
+    uint32_t* hbo = reinterpret_cast<uint32_t*>(hup + up_blob_off);
+    uint32_t qi = 0;
+    for (const CompiledQuery& cq : pb.queries) {
+        if (cq.status != 0) continue;
+        hbo[qi] = uint32_t(off);
+        const size_t packed = pack_blob(cq, idx, hup + off, dup + off, L.keys_base[qi], L.part_keys_off[qi], L.hist_offs[qi], L.fac_out_offs[qi], nullptr,
+                                        pb.profiled ? uint32_t((lay.off_stats - lay.off_hits) / 8 + qi) : 0u);  // 0: the kernels count nothing
+        if (packed != cq.blob_bytes) throw VelociError(ERR_DEVICE, "query blob changed size between compilation and packing (internal)");
+        off += packed;
+        ++qi;
+        ++P.tabs[table_of(cq)].n;  // pass 1: how many queries every table holds
     }
-    pb->d_blobs = dup;
-    pb->d_blob_off = reinterpret_cast<const uint32_t*>(dup + up_blob_off);
-    pb->d_facet_jobs = reinterpret_cast<const FacetJob*>(dup + up_jobs);
-    if (nq == 0) return pb;
+    hbo[nq] = uint32_t(off);
+    uint32_t at = 0;
+    for (ScanTable& t : P.tabs) {  // ... which places them
+        t.span_base = reinterpret_cast<uint32_t*>(hup + up_span) + at;
+        t.qmap = reinterpret_cast<uint32_t*>(hup + up_qmap) + at;
+        t.d_span_base = reinterpret_cast<const uint32_t*>(dup + up_span) + at;
+        t.d_qmap = reinterpret_cast<const uint32_t*>(dup + up_qmap) + at;
+        at += t.n + 1;
+        t.n = 0;
+    }
+    qi = 0;
+    for (const CompiledQuery& cq : pb.queries) {  // pass 2: the tables' entries and the launch parameters
+        if (cq.status != 0) continue;
+        const uint32_t ti = table_of(cq);
+        ScanTable& t = P.tabs[ti];
+        t.span_base[t.n] = t.spans;
+        t.qmap[t.n++] = qi;
+        t.spans += cq.n_spans;
+        const uint32_t n_scatter = cq.simple_n - uint32_t(__builtin_popcount(sf_bitmap_mask(cq.simple_flags)));
+        switch (cq.kclass) {
+            case K_SCAN_WIDE:
+                P.leaves_wide = std::max<uint32_t>(P.leaves_wide, cq.wide.n_leaves);
+                P.scatter_wide = std::max<uint32_t>(P.scatter_wide, cq.wide.n_leaves - uint32_t(__builtin_popcount(cq.wide.bitmap_mask)));
+                break;
+            case K_SCAN_RICH:
+                P.facets_rich = P.facets_rich || !cq.facets.empty();
+                P.scatter_rich = std::max<uint32_t>(P.scatter_rich, n_scatter + cq.simple2.n_side);
+                break;
+            case K_SCAN_UNION: P.union_has_or = P.union_has_or || cq.simple_n > 1; break;
+            case K_SCAN_PROBE: {
+                ScanPlan::ProbeParams& pp = P.probe[ti - T_PROBE];
+                pp.na_seen |= 1u << uint32_t(__builtin_popcount(sf_array_mask(cq.simple_flags)));
+                pp.arr_slot = std::max(pp.arr_slot, cq.probe_arr_gran * 4u);
+                P.any_probe = true;
+                break;
+            }
+            case K_SCAN_AND: P.scatter_and = std::max(P.scatter_and, n_scatter); break;
+            case K_SCAN_SIMPLE: P.scatter_simple = std::max(P.scatter_simple, n_scatter); break;
+            default: break;
+        }
+        pb.qclass.push_back(uint8_t(cq.kclass));
+        P.cls_layout[cq.kclass] += cq.layout_bytes;
+        P.cls_algo[cq.kclass] += cq.algorithmic_bytes;
+        P.cls_q[cq.kclass] += 1;
+        ++qi;
+    }
+    for (ScanTable& t : P.tabs) t.span_base[t.n] = t.spans;
+    if (!pb.facet_jobs.empty()) std::memcpy(hup + up_jobs, pb.facet_jobs.data(), pb.facet_jobs.size() * sizeof(FacetJob));
+    pb.d_blobs = dup;
+    pb.d_blob_off = reinterpret_cast<const uint32_t*>(dup + up_blob_off);
+    pb.d_facet_jobs = reinterpret_cast<const FacetJob*>(dup + up_jobs);
+    return P;
+}
 
-    const double t_packed = now_ms();
-    VQ_HIP(hipMemcpyAsync(dup, hup, up_bytes, hipMemcpyHostToDevice, st));
-    ws.d_span_keys.ensure(size_t(total_span_keys) * 8 + 16);
+// Upload, the batch's partial, then one launch per scan table that holds spans, k_merge_spans behind them, and the event finish_batch waits for
+static void launch_scans(const Index& idx, PartialBatch& pb, const BatchLayout& L, const ScanPlan& P, int64_t arena_offset) {
+    Workspace& ws = *pb.ws;
+    const PartialLayout& lay = pb.layout;
+    hipStream_t st = idx.stream;
+    VQ_HIP(hipMemcpyAsync(ws.d_up.as<uint8_t>(), ws.h_up.as<uint8_t>(), P.up_bytes, hipMemcpyHostToDevice, st));
+    ws.d_span_keys.ensure(size_t(L.total_span_keys) * 8 + 16);
     if (arena_offset >= 0) {  // a chunk of a sharded step with one collective: its partial lives in the index's arena
         if (size_t(arena_offset) % 256 || size_t(arena_offset) + lay.bytes > Index::kArenaBytes)
             throw VelociError(ERR_UNSUPPORTED, "partial arena: the step's partials do not fit (" + std::to_string(size_t(arena_offset) + lay.bytes) + " bytes)");
         idx.arena.ensure(Index::kArenaBytes);
-        pb->d_partial = idx.arena.as<uint8_t>() + arena_offset;
+        pb.d_partial = idx.arena.as<uint8_t>() + arena_offset;
     } else {
         ws.d_partial.ensure(lay.bytes);
-        pb->d_partial = ws.d_partial.as<uint8_t>();
+        pb.d_partial = ws.d_partial.as<uint8_t>();
     }
-    VQ_HIP(hipMemsetAsync(pb->d_partial, 0, lay.bytes, st));
+    VQ_HIP(hipMemsetAsync(pb.d_partial, 0, lay.bytes, st));
 
-    // ---- the scan
+    // what the launches are sized by, over ALL device queries of the batch (k_tile_scan's descriptor and list-table room too, whoever it serves)
     uint32_t max_top_k = 1;
-    for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0) max_top_k = std::max(max_top_k, pb->queries[i].top_k);
     uint32_t desc_cap = 0;  // bytes of the largest query descriptor (staged into LDS by every workgroup)
-    for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0) {
-            desc_cap = std::max(desc_cap, uint32_t(pb->queries[i].desc_bytes));
-        }
-    desc_cap = uint32_t(align_up(desc_cap, 16));
     bool facets_generic = false;  // k_tile_scan queries with facets: room for the LDS counter cache behind the descriptor
     static const bool no_facet_cache = std::getenv("VQ_NO_FACET_CACHE") != nullptr;
-    for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0 && pb->queries[i].kclass == K_TILE_SCAN && !pb->queries[i].facets.empty()) facets_generic = !no_facet_cache;
+    for (const CompiledQuery& cq : pb.queries) {
+        if (cq.status != 0) continue;
+        max_top_k = std::max(max_top_k, cq.top_k);
+        desc_cap = std::max(desc_cap, uint32_t(cq.desc_bytes));
+        if (cq.kclass == K_TILE_SCAN && !cq.facets.empty()) facets_generic = !no_facet_cache;
+    }
+    desc_cap = uint32_t(align_up(desc_cap, 16));
     if (facets_generic) desc_cap += 2 * 1024 * 4;
     static const uint32_t cand_min = [] {
         const char* e = std::getenv("VQ_CAND_CAP");  // (a small buffer is pruned — and its threshold raised — sooner: 64 beats 256 by 2-7 %, 32 beats 64 by 1-2 %)
@@ -1581,108 +1619,117 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     }();
     uint32_t cand_cap = cand_min;  // power of two >= 2 * top_k: candidate keys a workgroup keeps in LDS
     while (cand_cap < 2 * max_top_k) cand_cap <<= 1;
-    const uint32_t list_table = (std::max<uint32_t>(max_lists, 2) + 1u) & ~1u;  // k_tile_scan sizes its per-list LDS arrays to the launch's longest list table
+    const uint32_t list_table = (std::max<uint32_t>(L.max_lists, 2) + 1u) & ~1u;  // k_tile_scan sizes its per-list LDS arrays to the launch's longest list table
     static const bool tile_queue = std::getenv("VQ_NO_QUEUE") == nullptr;  // k_tile_scan: survivors of several tiles share a scoring round
-    for (size_t i = 0; i < n; ++i)
-        if (pb->queries[i].status == 0 && pb->queries[i].kclass == K_TILE_SCAN)
-            lds_bytes = std::max(lds_bytes, tile_scan_lds_bytes(uint32_t(pb->queries[i].lists.size()) + pb->queries[i].n_temps, uint32_t(pb->queries[i].lists.size()), pb->queries[i].tile_words, stack_depth, cand_cap, desc_cap, tile_queue && !pb->queries[i].simple_n, list_table));
+    size_t lds_bytes = 0;
+    for (const CompiledQuery& cq : pb.queries)
+        if (cq.status == 0 && cq.kclass == K_TILE_SCAN)
+            lds_bytes = std::max(lds_bytes, tile_scan_lds_bytes(uint32_t(cq.lists.size()) + cq.n_temps, uint32_t(cq.lists.size()), cq.tile_words, L.stack_depth, cand_cap, desc_cap,
+                                                                tile_queue && !cq.simple_n, list_table));
     if (lds_bytes > 160 * 1024) throw VelociError(ERR_UNSUPPORTED, "LDS tile larger than 160 KiB");
-    const bool prof = pb->profiled;
-    auto hits_ptr = reinterpret_cast<unsigned long long*>(pb->d_partial + lay.off_hits);
-    auto hist_ptr = reinterpret_cast<uint32_t*>(pb->d_partial + lay.off_hist);
+
+    auto hits_ptr = reinterpret_cast<unsigned long long*>(pb.d_partial + lay.off_hits);
+    auto hist_ptr = reinterpret_cast<uint32_t*>(pb.d_partial + lay.off_hist);
     auto keys_ptr = ws.d_span_keys.as<unsigned long long>();
-    auto d_span = [&](const ScanTable& t) { return reinterpret_cast<const uint32_t*>(dup + up_span) + t.first; };
-    auto d_qmap = [&](const ScanTable& t) { return reinterpret_cast<const uint32_t*>(dup + up_qmap) + t.first; };
-    auto timer = [&](int k) { return LaunchTimer(prof, ws, st, k, cls_layout[k], cls_algo[k], cls_q[k]); };
-    if (const ScanTable& t = tabs[T_LEAF_F32]; t.spans) {
-        auto lt = timer(K_SCAN_LEAF_F32);
-        launch_scan_leaf_f32(st, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
-    }
-    VQ_HIP(hipGetLastError());
-    if (const ScanTable& t = tabs[T_RICH]; t.spans) {
-        auto lt = timer(K_SCAN_RICH);
-        launch_scan_simple(st, true, scatter_rich, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr, facets_rich);
-    }
-    VQ_HIP(hipGetLastError());
-    if (any_probe) {  // (one timer over the shape kernels: the profile class is the sum of them)
-        auto lt = timer(K_SCAN_PROBE);
+    // one launch per table that holds spans, timed as its profile class, the launch error taken behind each
+    auto scan = [&](uint32_t table, int k, auto&& launch) {
+        if (const ScanTable& t = P.tabs[table]; t.spans) {
+            LaunchTimer lt(pb.profiled, ws, st, k, P.cls_layout[k], P.cls_algo[k], P.cls_q[k]);
+            launch(t);
+        }
+        VQ_HIP(hipGetLastError());
+    };
+    scan(T_LEAF_F32, K_SCAN_LEAF_F32, [&](const ScanTable& t) { launch_scan_leaf_f32(st, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr); });
+    scan(T_RICH, K_SCAN_RICH, [&](const ScanTable& t) { launch_scan_simple(st, true, P.scatter_rich, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr, P.facets_rich); });
+    if (P.any_probe) {  // (one timer over the shape kernels: the profile class is the sum of them)
+        LaunchTimer lt(pb.profiled, ws, st, K_SCAN_PROBE, P.cls_layout[K_SCAN_PROBE], P.cls_algo[K_SCAN_PROBE], P.cls_q[K_SCAN_PROBE]);
         static const bool trace = std::getenv("VQ_PROBE_TRACE") != nullptr;  // tools: what every shape kernel of a launch was given
         for (uint32_t c = 0; c < kProbeShapes; ++c)
-            if (const ScanTable& t = tabs[T_PROBE + c]; t.spans && trace)
+            if (const ScanTable& t = P.tabs[T_PROBE + c]; t.spans && trace)
                 std::fprintf(stderr, "probe launch: shape %u, %u queries, %u spans, array slot %u words (fullest tile: %u granules), NA seen 0x%x\n", c, t.n, t.spans,
-                             probe[c].arr_slot, probe[c].arr_slot / 4, probe[c].na_seen);
+                             P.probe[c].arr_slot, P.probe[c].arr_slot / 4, P.probe[c].na_seen);
         for (uint32_t c = 0; c < kProbeShapes; ++c)
-            if (const ScanTable& t = tabs[T_PROBE + c]; t.spans)
-                launch_scan_probe_shape(st, c, probe[c].na_seen, probe[c].arr_slot, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
+            if (const ScanTable& t = P.tabs[T_PROBE + c]; t.spans)
+                launch_scan_probe_shape(st, c, P.probe[c].na_seen, P.probe[c].arr_slot, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr);
     }
     VQ_HIP(hipGetLastError());
-    if (const ScanTable& t = tabs[T_AND]; t.spans) {
-        auto lt = timer(K_SCAN_AND);
-        launch_scan_simple(st, false, scatter_and, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
-    }
-    VQ_HIP(hipGetLastError());
+    scan(T_AND, K_SCAN_AND, [&](const ScanTable& t) { launch_scan_simple(st, false, P.scatter_and, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr); });
     // (16384-doc tiles pay off for ORs too once LDS no longer bounds the occupancy)
-    if (const ScanTable& t = tabs[T_SIMPLE]; t.spans) {
-        auto lt = timer(K_SCAN_SIMPLE);
-        launch_scan_simple(st, false, scatter_simple, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr);
-    }
-    VQ_HIP(hipGetLastError());
-    if (const ScanTable& t = tabs[T_UNION]; t.spans) {
-        auto lt = timer(K_SCAN_UNION);
-        launch_scan_union(st, union_has_or, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
-    }
-    VQ_HIP(hipGetLastError());
-    if (const ScanTable& t = tabs[T_WIDE]; t.spans) {
-        auto lt = timer(K_SCAN_WIDE);
-        launch_scan_wide(st, leaves_wide, scatter_wide, t.spans, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, cand_cap, keys_ptr, hits_ptr);
-    }
-    VQ_HIP(hipGetLastError());
-    if (const ScanTable& t = tabs[T_TILE]; t.spans) {
-        auto lt = timer(K_TILE_SCAN);
-        launch_tile_scan(st, t.spans, lds_bytes, pb->d_blobs, pb->d_blob_off, d_span(t), d_qmap(t), t.n, stack_depth, cand_cap, desc_cap, keys_ptr, hits_ptr, hist_ptr, tile_queue,
-                         list_table, facets_generic);
-    }
-    VQ_HIP(hipGetLastError());
+    scan(T_SIMPLE, K_SCAN_SIMPLE, [&](const ScanTable& t) { launch_scan_simple(st, false, P.scatter_simple, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr, hist_ptr); });
+    scan(T_UNION, K_SCAN_UNION, [&](const ScanTable& t) { launch_scan_union(st, P.union_has_or, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr); });
+    scan(T_WIDE, K_SCAN_WIDE, [&](const ScanTable& t) { launch_scan_wide(st, P.leaves_wide, P.scatter_wide, t.spans, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, cand_cap, keys_ptr, hits_ptr); });
+    scan(T_TILE, K_TILE_SCAN, [&](const ScanTable& t) { launch_tile_scan(st, t.spans, lds_bytes, pb.d_blobs, pb.d_blob_off, t.d_span_base, t.d_qmap, t.n, L.stack_depth, cand_cap, desc_cap, keys_ptr, hits_ptr, hist_ptr, tile_queue, list_table, facets_generic); });
     {
-        LaunchTimer t(prof, ws, st, K_MERGE_SPANS, total_span_keys * 8 + total_keys * 8, total_span_keys * 8 + total_keys * 8, nq);
-        launch_merge_spans(st, nq, pb->d_blobs, pb->d_blob_off, keys_ptr, reinterpret_cast<unsigned long long*>(pb->d_partial + lay.off_keys));
+        LaunchTimer t(pb.profiled, ws, st, K_MERGE_SPANS, L.total_span_keys * 8 + L.total_keys * 8, L.total_span_keys * 8 + L.total_keys * 8, L.nq);
+        launch_merge_spans(st, L.nq, pb.d_blobs, pb.d_blob_off, keys_ptr, reinterpret_cast<unsigned long long*>(pb.d_partial + lay.off_keys));
     }
     VQ_HIP(hipGetLastError());
     VQ_HIP(hipEventRecord(ws.ev_done, st));
-    pb->launched = true;
-    if (timing_enabled())
-        std::fprintf(stderr, "[vq timing] n=%zu compile %.3f ms (dictionary scans %.3f [%zu probes], pass 1 %.3f, unions %.3f [%zu jobs], pass 2 %.3f), range jobs %.3f [%zu], spans generic/simple/and/rich/union %u/%u/%u/%u/%u, pack+launch %.3f ms\n", n,
-                     t_compiled - t_start, t_probes - t_start, fuzzy.size(), t_pass1 - t_probes, t_unions - t_pass1, unions.size(), t_compiled - t_ranges,
-                     t_ranges - t_unions, ranges.size(), tabs[T_TILE].spans, tabs[T_SIMPLE].spans, tabs[T_AND].spans, tabs[T_RICH].spans, tabs[T_UNION].spans + tabs[T_LEAF_F32].spans, now_ms() - t_compiled);
-    if (timing_enabled())
-        std::fprintf(stderr, "[vq timing] pack+launch: span sizing + layout %.3f, blobs + tables %.3f, upload + launches %.3f ms\n", t_layout - t_compiled, t_packed - t_layout, now_ms() - t_packed);
-    if (timing_enabled()) {  // thread-time inside compile_query since the last batch (all passes, all threads)
-        uint64_t v[16];
-        for (int k = 0; k < 16; ++k) v[k] = g_compile_ns[k].exchange(0);
-        if (std::getenv("VQ_TIMING_SUB")) {
-            std::fprintf(stderr, "[vq timing] inside 1:n resolve (thread-ms; 6 value-id gather, 7 sort, 8 pairs, 9 order check + layers):");
-            for (int k = 6; k < 10; ++k) std::fprintf(stderr, " [%d] %.3f", k, v[k] * 1e-6);
-            std::fprintf(stderr, "\n");
-        }
-        std::fprintf(stderr, "[vq timing] compile thread-ms: total %.3f = dictionary lookups %.3f + 1:n resolve %.3f + 1:n layers %.3f + leaf lists %.3f + rest %.3f; longest request %.3f\n", v[5] * 1e-6,
-                     v[0] * 1e-6, v[1] * 1e-6, (v[2] - v[1]) * 1e-6, v[3] * 1e-6, (double(v[5]) - double(v[0]) - double(v[2]) - double(v[3])) * 1e-6, v[4] * 1e-6);
+    pb.launched = true;
+}
+
+// VQ_TIMING: the step's host time by phase (tools/compile_scaling.sh cuts columns out of the "n=" line)
+static void report_timing(size_t n, double t_start, const CompileReport& c, double t_layout, double t_packed, const ScanTable* tabs) {
+    if (!timing_enabled()) return;
+    std::fprintf(stderr, "[vq timing] n=%zu compile %.3f ms (dictionary scans %.3f [%zu probes], pass 1 %.3f, unions %.3f [%zu jobs], pass 2 %.3f), range jobs %.3f [%zu], spans generic/simple/and/rich/union %u/%u/%u/%u/%u, pack+launch %.3f ms\n", n,
+                 c.t_compiled - t_start, c.t_probes - t_start, c.probes, c.t_pass1 - c.t_probes, c.t_unions - c.t_pass1, c.unions, c.t_compiled - c.t_ranges,
+                 c.t_ranges - c.t_unions, c.ranges, tabs[T_TILE].spans, tabs[T_SIMPLE].spans, tabs[T_AND].spans, tabs[T_RICH].spans, tabs[T_UNION].spans + tabs[T_LEAF_F32].spans, now_ms() - c.t_compiled);
+    std::fprintf(stderr, "[vq timing] pack+launch: span sizing + layout %.3f, blobs + tables %.3f, upload + launches %.3f ms\n", t_layout - c.t_compiled, t_packed - t_layout, now_ms() - t_packed);
+    // thread-time inside compile_query since the last batch (all passes, all threads)
+    uint64_t v[16];
+    for (int k = 0; k < 16; ++k) v[k] = g_compile_ns[k].exchange(0);
+    if (std::getenv("VQ_TIMING_SUB")) {
+        std::fprintf(stderr, "[vq timing] inside 1:n resolve (thread-ms; 6 value-id gather, 7 sort, 8 pairs, 9 order check + layers):");
+        for (int k = 6; k < 10; ++k) std::fprintf(stderr, " [%d] %.3f", k, v[k] * 1e-6);
+        std::fprintf(stderr, "\n");
     }
+    std::fprintf(stderr, "[vq timing] compile thread-ms: total %.3f = dictionary lookups %.3f + 1:n resolve %.3f + 1:n layers %.3f + leaf lists %.3f + rest %.3f; longest request %.3f\n", v[5] * 1e-6,
+                 v[0] * 1e-6, v[1] * 1e-6, (v[2] - v[1]) * 1e-6, v[3] * 1e-6, (double(v[5]) - double(v[0]) - double(v[2]) - double(v[3])) * 1e-6, v[4] * 1e-6);
+}
+
+std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot, int64_t arena_offset) {
+    const double t_start = now_ms();
+    auto pb = std::make_unique<PartialBatch>();
+    pb->index = &idx;
+    pb->reqs.assign(reqs, reqs + n);
+    pb->t0 = std::chrono::steady_clock::now();
+    acquire_workspace(idx, *pb, slot);
+    VQ_HIP(hipSetDevice(idx.device));
+    Workspace& ws = *pb->ws;
+    ws.timed.clear();
+    ws.ev_used = 0;
+    pb->profiled = idx.profile.enabled;
+
+    const CompileReport compiled = compile_batch(idx, ws, *pb, reqs, n, idx.stream);
+    size_spans(pb->queries);
+    const BatchLayout layout = plan_layout(idx, *pb);
+    const double t_layout = now_ms();
+    const ScanPlan plan = pack_upload(idx, *pb, layout);
+    if (layout.nq == 0) return pb;  // nothing compiled: there is nothing to launch (finish_batch reports the requests' errors)
+    const double t_packed = now_ms();
+    launch_scans(idx, *pb, layout, plan, arena_offset);
+    report_timing(n, t_start, compiled, t_layout, t_packed, plan.tabs);
     return pb;
+}
+
+// The dictionary scans of a suggest / highlight request, answered: on the next workspace in turn, on the pre-passes' stream
+static FuzzyTable run_suggest_probes(const Index& idx, const vqreq::Request& req) {
+    FuzzyTable fuzzy;
+    collect_suggest_probes(idx, req, fuzzy);
+    if (fuzzy.empty()) return fuzzy;
+    Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
+    std::unique_lock<std::mutex> lock(ws.mu);
+    ws.timed.clear();
+    ws.ev_used = 0;
+    run_fuzzy_probes(idx, ws, fuzzy, idx.pre_stream ? idx.pre_stream : idx.stream);
+    return fuzzy;
 }
 
 // suggest_multi (search_field.rs:194-219): dictionary side only — the parts' matched terms, equal texts merged keeping the best score, ranked
 std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& req) {
     if (!req.suggest) throw VelociError(ERR_INVALID_REQUEST, "only suggest allowed in suggest function");
     VQ_HIP(hipSetDevice(idx.device));
-    FuzzyTable fuzzy;
-    collect_suggest_probes(idx, req, fuzzy);
-    if (!fuzzy.empty()) {
-        Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
-        std::unique_lock<std::mutex> lock(ws.mu);
-        ws.timed.clear();
-        ws.ev_used = 0;
-        run_fuzzy_probes(idx, ws, fuzzy, idx.pre_stream ? idx.pre_stream : idx.stream);
-    }
+    const FuzzyTable fuzzy = run_suggest_probes(idx, req);
     std::vector<SuggestEntry> out;
     for (auto& part : *req.suggest) {
         auto one = suggest_part(idx, part, fuzzy.empty() ? nullptr : &fuzzy);
@@ -1709,15 +1756,7 @@ std::vector<SuggestEntry> run_highlight(const Index& idx, vqreq::RequestSearchPa
     VQ_HIP(hipSetDevice(idx.device));
     vqreq::Request probe_req;
     probe_req.suggest = std::vector<vqreq::RequestSearchPart>{part};
-    FuzzyTable fuzzy;
-    collect_suggest_probes(idx, probe_req, fuzzy);
-    if (!fuzzy.empty()) {
-        Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
-        std::unique_lock<std::mutex> lock(ws.mu);
-        ws.timed.clear();
-        ws.ev_used = 0;
-        run_fuzzy_probes(idx, ws, fuzzy, idx.pre_stream ? idx.pre_stream : idx.stream);
-    }
+    const FuzzyTable fuzzy = run_suggest_probes(idx, probe_req);
     std::vector<SuggestEntry> out = highlight_part(idx, part, fuzzy.empty() ? nullptr : &fuzzy);
     std::stable_sort(out.begin(), out.end(), [](const SuggestEntry& a, const SuggestEntry& b) { return a.score > b.score; });  // :189
     const size_t skip = std::min(part.skip.value_or(0), out.size());  // apply_top_skip, search.rs:230-239

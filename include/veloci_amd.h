@@ -225,6 +225,13 @@ const char* vq_suggest_text(const vq_suggest_result*, size_t i);
 float vq_suggest_score(const vq_suggest_result*, size_t i);
 uint32_t vq_suggest_term_id(const vq_suggest_result*, size_t i);
 void vq_suggest_free(vq_suggest_result*);
+/* n independent suggest requests (each text as vq_suggest_json takes it: a Request with "suggest" parts, or a bare RequestSearchPart)
+ * answered as one device batch.  out[i] receives request i's result, or NULL with status[i] != VQ_OK; the text of the first failing
+ * request is in vq_last_error.  Returns VQ_OK when the batch ran.  Every out[i] equals what vq_suggest_json returns for json[i].
+ * The dictionary scans of all requests run together (equal probes once).  A part with its own `top` whose top + skip is at most 1848 has
+ * the reference's top-n loop run on the device (k_dict_topn) and only that loop's final buffer copied back; VQ_NO_SUGGEST_TOPN=1 keeps
+ * every part on the route that copies all matches back. */
+int vq_suggest_batch(const vq_index*, const char* const* json, const size_t* len, size_t n, vq_suggest_result** out, int* status);
 
 /* ---------------------------------------------------------------- highlight
  * == search_field::highlight(persistence, &mut part) (src/search/search_field.rs:233-245): `json` is a bare RequestSearchPart with
@@ -368,6 +375,13 @@ uint32_t vq_debug_div100_mismatches(void);
 /* Requests of this index that were run a second time on the exact kernels because the short cut of a speculative one could not be confirmed:
  * an OR of the shape k_scan_probe_or takes ranks only the docs that hold its rarest term and is confirmed by the k-th key it returns. */
 uint64_t vq_index_speculative_reruns(const vq_index*);
+/* Totals of this index's vq_suggest_batch calls since it was built: probes answered by k_dict_topn, and match records copied back from the
+ * device (a top-n probe counts min(its matches, top + skip + 200) entries, every other probe its matches).  Either pointer may be NULL. */
+void vq_index_suggest_topn_probes(const vq_index*, uint64_t* topn_probes, uint64_t* records_copied_back);
+/* k_dict_topn (the top-n loop of search_field.rs:322-333 + sort.rs:25-34) on one crafted stream: n (term, class) pairs in term-id order, class =
+ * 2 * distance + prefix_matches (< 512), top_n in 1 .. 1848.  Writes the loop's final buffer in buffer order (the out arrays take top_n + 200
+ * entries) and its length.  0; -1 without a device; -2 for arguments outside these ranges. */
+int vq_debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t n, uint32_t top_n, uint32_t* out_terms, uint32_t* out_classes, uint32_t* out_n);
 
 /* The facet selection kernels (k_facet_select / k_facet_select_wide: facet.rs:19-23, count descending; ties by value id ascending) on a
  * caller's histogram of `num_values` counts, placed `misalign` (0-3) counters behind a 16-byte boundary as inside a batch's histogram area:

@@ -237,7 +237,7 @@ void dump_parts(std::string& s, const std::optional<std::vector<vqreq::RequestSe
 extern "C" {
 
 const char* vq_last_error(void) { return g_err.c_str(); }
-const char* vq_version(void) { return "veloci_amd 0.3 (gfx950)"; }
+const char* vq_version(void) { return "veloci_amd 0.4 (gfx950)"; }
 /* self-check (tests): inputs for which the kernels' fast a/100 differs from the correctly rounded division, over all f16 values */
 uint32_t vq_debug_div100_mismatches(void) { return vq::debug_div100_mismatches(); }
 /* tools/probe_occupancy.py (like the stamp readers below: exported, not part of the header): LDS bytes of a probe kernel's one-wave workgroup (shape: kProbe* of kernels.hpp; nd / na operands beside the cover / probed as arrays; arr_slot words per
@@ -249,6 +249,22 @@ uint32_t vq_debug_probe_occupancy(uint32_t shape, uint32_t nd, uint32_t na, uint
 }
 /* tests, tools: requests that ran a second time because a speculative route's result could not be confirmed (k_scan_probe_or) */
 uint64_t vq_index_speculative_reruns(const vq_index* index) { return index ? index->idx->or_reruns.load() : 0; }
+/* tests, tools: since the index was built, the probes of suggest batches that k_dict_topn answered and the match records those batches copied back
+   (a top-n probe: min(its matches, top + skip + 200) entries) */
+void vq_index_suggest_topn_probes(const vq_index* index, uint64_t* topn_probes, uint64_t* records_copied_back) {
+    if (topn_probes) *topn_probes = index ? index->idx->suggest_topn_probes.load() : 0;
+    if (records_copied_back) *records_copied_back = index ? index->idx->suggest_records_back.load() : 0;
+}
+/* self-check (tests): k_dict_topn on one crafted stream of (term, class) in id order -> its final buffer in buffer order (out_terms / out_classes
+   take top_n + 200 entries).  0; -1 without a device; -2 for arguments the kernel does not take */
+int vq_debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t n, uint32_t top_n, uint32_t* out_terms, uint32_t* out_classes, uint32_t* out_n) {
+    if ((n && (!terms || !classes)) || !out_terms || !out_classes || !out_n || top_n == 0 || top_n > vq::kTopnMax) return -2;
+    for (uint32_t i = 0; i < n; ++i)
+        if (classes[i] >= vq::kTopnClasses) return -2;
+    uint16_t ord[vq::kTopnClasses];
+    vq::topn_class_ords(ord);
+    return vq::debug_dict_topn(terms, classes, n, top_n, ord, out_terms, out_classes, out_n);
+}
 /* self-check (tests): the facet top-`top` kernels on a caller's histogram */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts) {
     if (!hist || !out_values || !out_counts) return -1;
@@ -606,23 +622,28 @@ const char* vq_result_why_found_info_json(const vq_result* r) {
 void vq_result_free(vq_result* r) { delete r; }
 
 // ------------------------------------------------------------------ suggest
+// the text of a suggest request: a Request with "suggest" parts, or a bare RequestSearchPart
+static Request suggest_request_from_text(const char* json, size_t len) {
+    Request req;
+    try {
+        vqjson::Value v = vqjson::parse(json, len);
+        if (v.is_object() && v.get("suggest")) req = vqreq::request_from_json(v);
+        else {  // a bare RequestSearchPart: search_field::suggest (:221-231), top / skip are the part's
+            vqreq::RequestSearchPart part = vqreq::search_part_from_json(v);
+            req.suggest = std::vector<vqreq::RequestSearchPart>{part};
+            req.top = part.top;
+            req.skip = part.skip;
+        }
+    } catch (const vqjson::ParseError& e) {
+        throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+    }
+    return req;
+}
 int vq_suggest_json(const vq_index* index, const char* json, size_t len, vq_suggest_result** out) {
     return guard([&] {
         if (!index || !json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_suggest_json: null argument");
         *out = nullptr;
-        Request req;
-        try {
-            vqjson::Value v = vqjson::parse(json, len);
-            if (v.is_object() && v.get("suggest")) req = vqreq::request_from_json(v);
-            else {  // a bare RequestSearchPart: search_field::suggest (:221-231), top / skip are the part's
-                vqreq::RequestSearchPart part = vqreq::search_part_from_json(v);
-                req.suggest = std::vector<vqreq::RequestSearchPart>{part};
-                req.top = part.top;
-                req.skip = part.skip;
-            }
-        } catch (const vqjson::ParseError& e) {
-            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
-        }
+        const Request req = suggest_request_from_text(json, len);
         auto* r = new vq_suggest_result();
         try {
             r->e = run_suggest(*index->idx, req);
@@ -632,6 +653,42 @@ int vq_suggest_json(const vq_index* index, const char* json, size_t len, vq_sugg
         }
         *out = r;
     });
+}
+int vq_suggest_batch(const vq_index* index, const char* const* json, const size_t* len, size_t n, vq_suggest_result** out, int* status) {
+    std::string first_error;
+    const int rc = guard([&] {
+        if (!index || (n && (!json || !len || !out))) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_suggest_batch: null argument");
+        for (size_t i = 0; i < n; ++i) out[i] = nullptr;
+        std::vector<Request> parsed(n);
+        std::vector<const Request*> reqs(n, nullptr);
+        std::vector<int> parse_status(n, 0);
+        std::vector<std::string> parse_error(n);
+        for (size_t i = 0; i < n; ++i) {
+            try {
+                if (!json[i]) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_suggest_batch: null request text");
+                parsed[i] = suggest_request_from_text(json[i], len[i]);
+                reqs[i] = &parsed[i];
+            } catch (const VelociError& e) {
+                parse_status[i] = e.code;
+                parse_error[i] = e.what();
+            }
+        }
+        std::vector<std::vector<SuggestEntry>> results;
+        std::vector<int> st;
+        std::vector<std::string> errs;
+        run_suggest_batch(*index->idx, reqs.data(), n, results, st, errs);
+        for (size_t i = 0; i < n; ++i) {
+            const int code = parse_status[i] ? parse_status[i] : st[i];
+            if (status) status[i] = code;
+            if (code == 0) {
+                auto* r = new vq_suggest_result();
+                r->e = std::move(results[i]);
+                out[i] = r;
+            } else if (first_error.empty()) first_error = parse_status[i] ? parse_error[i] : errs[i];
+        }
+    });
+    if (rc == VQ_OK && !first_error.empty()) g_err = first_error;  // (the batch ran: the first failing request's text)
+    return rc;
 }
 int vq_highlight_json(const vq_index* index, const char* json, size_t len, vq_suggest_result** out) {
     return guard([&]() {

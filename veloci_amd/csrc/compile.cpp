@@ -406,7 +406,15 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             else cand = regex_candidates(dict, p);
         } else if (scan) {  // match set computed on the device before compilation (k_dict_scan), ascending == FST stream order
             const FuzzyProbe* fp = nullptr;
-            if (fuzzy) {
+            if (fuzzy && topn_probes && p.top) {
+                // A top-n probe of a suggest batch: `matches` / `scores` are the FINAL buffer of the loop below, made by k_dict_topn over the
+                // same matches in the same order, and they pass through that loop unchanged.  The loop's cut needs size == top_n + 200 BEFORE a
+                // push, which at most top_n + 200 entries in all never reach; so worst_score never rises, nothing is skipped, and the stable
+                // sort behind the loop sees the very vector the full route would have built.
+                auto it = fuzzy->find(topn_key(p));
+                if (it != fuzzy->end() && it->second.top_n != 0) fp = &it->second;
+            }
+            if (fuzzy && !fp) {
                 auto it = fuzzy->find(fuzzy_key(p));
                 if (it != fuzzy->end()) fp = &it->second;
             }
@@ -455,7 +463,9 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                     if (!l.hits_scores.empty() && l.hits_scores.size() == top_n_search + 200) {  // sort.rs:24-34
                         std::sort(l.hits_scores.begin(), l.hits_scores.end(), [](auto& a, auto& b) { return a.second == b.second ? a.first > b.first : a.second > b.second; });
                         l.hits_scores.resize(top_n_search);
-                        worst_score = l.hits_scores.back().second;
+                        // (top + skip == 0 keeps nothing: the reference panics on its empty vector; here the bound stays where it was and the
+                        // truncation behind the loop leaves no hit)
+                        if (!l.hits_scores.empty()) worst_score = l.hits_scores.back().second;
                     }
                 }
                 l.hits_scores.push_back({id, score});
@@ -2517,9 +2527,11 @@ size_t debug_sort_unique(uint32_t* ids, size_t n) {  // (tests: the three regime
 
 // suggest (search_field.rs:194-219): one part's matched terms with lower-cased texts and scores — get_term_ids_in_field with get_scores,
 // return_term and return_term_lowercase; the dictionary scan of a fuzzy / prefix part has run on the device (`fuzzy`).
-std::vector<SuggestEntry> suggest_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
+std::vector<SuggestEntry> suggest_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy, bool topn_probes) {
     Request dummy;
-    Compiler c(idx, dummy, CompileInputs{fuzzy});
+    CompileInputs in{fuzzy};
+    in.topn_probes = topn_probes;
+    Compiler c(idx, dummy, in);
     Leaf l;
     l.part = &part;
     l.get_scores = true;
@@ -2763,6 +2775,29 @@ std::string fuzzy_key(const RequestSearchPart& p) {
     return k;
 }
 bool needs_dictionary_scan(const RequestSearchPart& p) { return !p.terms.empty() && !p.is_regex && (clamped_lev(p) != 0 || p.starts_with); }
+std::string topn_key(const RequestSearchPart& p) { return fuzzy_key(p) + "#" + std::to_string(p.top.value_or(10)) + "+" + std::to_string(p.skip.value_or(0)); }
+
+// VQ_NO_SUGGEST_TOPN=1: every part of a suggest batch keeps the full route (all matches back, the top-n loop on the host)
+static bool suggest_topn_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("VQ_NO_SUGGEST_TOPN");
+        return !(e && *e && std::string(e) != "0");
+    }();
+    return on;
+}
+// what run_fuzzy_probes decides per probe: k_dict_scan takes a 16-bit image and a query of <= 64 code points below U+10000, every other probe
+// goes to k_dict_scan_wide; either scores a hit itself when the lower-cased term has at most 64 code points (k_dict_scan: all below U+10000)
+// and the lower-cased image is exact
+bool probe_scored_on_device(const Index& idx, const FuzzyProbe& fp) {
+    const Dictionary& d = idx.dict.at(fp.path);
+    bool wide = d.char_bytes != 2 || fp.query.size() > 64;
+    for (uint32_t cp : fp.query) wide = wide || cp > 0xFFFFu;
+    const auto lcps = vqtext::decode_utf8(fp.lower_term);
+    bool ok = lcps.size() <= 64 && d.low_exact;
+    if (!wide)
+        for (uint32_t cp : lcps) ok = ok && cp <= 0xFFFFu;
+    return ok;
+}
 
 // VQ_NO_REGEX_DEVICE=1: every regex leaf stays on the host route
 static bool regex_device_enabled() {
@@ -2811,11 +2846,16 @@ static void probe_regex_part(const Index& idx, const RequestSearchPart& p, Fuzzy
     table.emplace(key, std::move(fp));
 }
 
-static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table) {
+// suggest_batch: a part with its own top whose top + skip fits k_dict_topn's buffer asks for a top-n probe (key: topn_key) when the device scores
+// its hits and neither distance can reach the u8 cap (lower-cased term below 255 bytes, every term of the dictionary below 200: then the
+// long-string branch of the scoring rule cannot occur either)
+static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table, bool suggest_batch = false) {
     if (p.is_regex) return probe_regex_part(idx, p, table);
     if (!needs_dictionary_scan(p)) return;
     const std::string key = fuzzy_key(p);
-    if (table.count(key)) return;
+    const size_t top_n = p.top.value_or(0) + p.skip.value_or(0);
+    const bool ask_topn = suggest_batch && suggest_topn_enabled() && p.top && top_n >= *p.top && top_n >= 1 && top_n <= kTopnMax;
+    if (table.count(ask_topn ? topn_key(p) : key)) return;
     FuzzyProbe fp;
     fp.key = key;
     fp.path = p.path;
@@ -2837,7 +2877,13 @@ static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable&
                    std::to_string(kDictMaxPattern) + ")";
     }
     for (uint32_t cp : cps) fp.query.push_back(fp.ci ? vqtext::lower_cp(cp) : cp);
-    table.emplace(key, std::move(fp));
+    if (ask_topn && fp.status == 0 && fp.lower_term.size() < 255 && dit->second.max_term_bytes < 200 && probe_scored_on_device(idx, fp)) {
+        fp.top_n = uint32_t(top_n);
+        fp.key = topn_key(p);
+        table.emplace(fp.key, std::move(fp));
+        return;
+    }
+    if (!table.count(key)) table.emplace(key, std::move(fp));
 }
 static void probe_tree(const Index& idx, const SearchRequest& r, FuzzyTable& table) {
     if (r.kind == SearchRequest::Search) probe_part(idx, r.part, table);
@@ -2859,6 +2905,11 @@ void score_fuzzy_probe(const Index& idx, FuzzyProbe& fp) {
 void collect_suggest_probes(const Index& idx, const Request& req, FuzzyTable& table) {
     if (req.suggest)
         for (auto& p : *req.suggest) probe_part(idx, p, table);
+}
+
+void collect_suggest_batch_probes(const Index& idx, const Request& req, FuzzyTable& table) {
+    if (req.suggest)
+        for (auto& p : *req.suggest) probe_part(idx, p, table, true);
 }
 
 void collect_fuzzy_probes(const Index& idx, const Request& req, FuzzyTable& table) {

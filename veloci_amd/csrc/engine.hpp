@@ -162,6 +162,7 @@ struct Dictionary {  // term dictionary of one text field
     std::unordered_map<std::string, std::vector<uint32_t>> lower_map;  // lowercase(term) -> ascending term ids (exact lookups)
     // device image for the fuzzy / prefix scan (k_dict_scan): one code point per element, raw and lower-cased per code point
     uint32_t char_bytes = 2;  // 2: every code point is below U+10000 (u16 image); 4: some term has one above U+FFFF (u32 image)
+    size_t max_term_bytes = 0;  // the longest term (the batched suggest's top-n route wants every term shorter than 200 bytes)
     bool low_exact = true;    // false: the lower-cased image is not str::to_lowercase of every term (U+0130): matches are scored on the host
     DevBuf d_off;             // u32 [T + 1]
     DevBuf d_raw;             // u16 or u32 (char_bytes)
@@ -191,9 +192,15 @@ struct FuzzyProbe {  // one dictionary scan of a batch (get_text_lines_from_fst,
     bool regex = false;               // a regex leaf whose pattern compiled (k_dict_regex): `dfa` is the probe, `matches` the result, scores stay with the host
     vqregex::Dfa dfa;
     bool answered = false;            // run_fuzzy_probes has filled `matches`
+    // > 0: a top-n probe of the batched suggest (top + skip of its part).  `matches` / `scores` are then NOT a match set: they are the final buffer
+    // of the reference's top-n loop (search_field.rs:322-333) in buffer order, at most top_n + 200 entries, made by k_dict_topn.  Its key carries
+    // top_n (topn_key), so nothing that looks a probe up by fuzzy_key finds it.
+    uint32_t top_n = 0;
+    uint32_t topn_copied = 0;  // entries copied back for it: min(its matches, top_n + 200)
 };
 using FuzzyTable = std::map<std::string, FuzzyProbe>;
 std::string fuzzy_key(const vqreq::RequestSearchPart& p);
+std::string topn_key(const vqreq::RequestSearchPart& p);  // fuzzy_key plus top + skip: the key of a part's top-n probe
 bool needs_dictionary_scan(const vqreq::RequestSearchPart& p);
 // The route of a regex part: its DFA when k_dict_regex takes it, else the reason it stays on the host.  Throws what the search would answer for
 // a part that cannot run at all (no terms, unknown field, invalid pattern).
@@ -209,13 +216,21 @@ struct SuggestEntry {  // search_field.rs:158 SuggestFieldResult = Vec<(String, 
     float score;
     uint32_t term_id;
 };
-std::vector<SuggestEntry> suggest_part(const Index& idx, const vqreq::RequestSearchPart& part, const FuzzyTable* fuzzy);
+// (topn_probes: `fuzzy` is the table of a suggest batch and may hold the part's top-n probe)
+std::vector<SuggestEntry> suggest_part(const Index& idx, const vqreq::RequestSearchPart& part, const FuzzyTable* fuzzy, bool topn_probes = false);
 void collect_suggest_probes(const Index& idx, const vqreq::Request& req, FuzzyTable& table);
+// the same for a request of a suggest batch: a part that qualifies gets a top-n probe instead of a full one
+void collect_suggest_batch_probes(const Index& idx, const vqreq::Request& req, FuzzyTable& table);
+void topn_class_ords(uint16_t* ord);  // k_dict_topn's class table (kTopnClasses entries), as the suggest batch uploads it
+bool probe_scored_on_device(const Index& idx, const FuzzyProbe& fp);  // run_fuzzy_probes' rule: the scan kernel scores the hits of this probe
 std::optional<std::string> highlight_text(const std::string& text, const std::vector<std::string>& terms, const vqreq::SnippetInfo& opt, bool tokenized);  // highlight_field.rs:92-146
 vqreq::Request page_request_after(const vqreq::Request& request, float score, uint32_t id);
 std::vector<SuggestEntry> highlight_part(const Index& idx, const vqreq::RequestSearchPart& part, const FuzzyTable* fuzzy);
 std::vector<SuggestEntry> run_highlight(const Index& idx, vqreq::RequestSearchPart part);  // search_field::highlight, search_field.rs:233-245
 std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& req);  // suggest_multi, search_field.rs:194-219
+// n suggest requests as one device batch (a null request, or one that fails, fails alone: status / errors); every result equals run_suggest's
+void run_suggest_batch(const Index& idx, const vqreq::Request* const* reqs, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
+                       std::vector<std::string>& errors);
 
 // A leaf whose expansion matched many terms is materialised before the scan (k_union, K2): union of the
 // terms' posting lists with the per-doc maximum of term_score * (f16 / 100).
@@ -430,7 +445,7 @@ constexpr int kWorkspaces = 4;  // batches in flight per index (host compile of 
 
 // Kernels the profiler accounts separately (vq_profile_json): the pre-passes, one entry per scan class, the merges.
 enum KernelId : int {
-    K_DICT_SCAN = 0, K_DICT_REGEX, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
+    K_DICT_SCAN = 0, K_DICT_REGEX, K_DICT_TOPN_GROUP, K_DICT_TOPN, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
     K_SCAN_WIDE, K_TILE_SCAN, K_MERGE_SPANS, K_FINALIZE, K_FACET_SELECT, K_LOCALITY, K_BOOST1N, K_COUNT_
 };
 extern const char* const kKernelNames[K_COUNT_];
@@ -459,6 +474,7 @@ struct Workspace {  // scratch of one in-flight batch
     DevBuf d_b1n_a, d_b1n_b, d_b1n_meta, d_b1n_tmp, d_b1n_docs, d_b1n_vals;                              // 1:n boost lists (K10)
     DevBuf d_probe_desc, d_probe_counts, d_probe_ids;                    // dictionary scans (k_dict_scan): kept, so that no hipFree synchronises the device mid-pipeline
     DevBuf d_regex_tabs;                                                 // regex probes (k_dict_regex): descriptors + table pool
+    DevBuf d_topn_sort, d_topn_tmp, d_topn_meta, d_topn_out;             // leaf top-n of a suggest batch (dict_topn.hip): keys + infos (unsorted, sorted), rocPRIM's storage, tables, buffers
 };
 
 struct KernelProfile {
@@ -522,6 +538,7 @@ struct Index {
         if (!sharded() || v.empty()) return;
         if (!allreduce_fn || allreduce_fn(allreduce_ctx, v.data(), v.size()) != 0) throw vqreq::VelociError(vqreq::ERR_DEVICE, "all-reduce over the shards failed");
     }
+    mutable std::atomic<uint64_t> suggest_topn_probes{0}, suggest_records_back{0};  // suggest batches: probes answered by k_dict_topn; match records copied back (tests, tools)
     mutable std::atomic<uint64_t> or_reruns{0};  // requests that ran a second time because k_scan_probe_or's short cut could not be confirmed (tests, tools)
     mutable std::unique_ptr<HostPool> pool;  // created on first use
     mutable std::mutex pool_mu;
@@ -685,6 +702,7 @@ struct CompileInputs {
     const RangeTable* ranges = nullptr;
     Boost1nCache* boost_cache = nullptr;
     const LocalityTable* localities = nullptr;
+    bool topn_probes = false;  // `fuzzy` may hold top-n probes (FuzzyProbe::top_n): only the batched suggest sets it, every other caller looks up by fuzzy_key alone
 };
 CompiledQuery compile_query(const Index& idx, const vqreq::Request& req, const CompileInputs& in = {});
 void run_locality_jobs(const Index& idx, Workspace& ws, LocalityTable& table, hipStream_t st);

@@ -39,7 +39,7 @@ static bool timing_enabled() {
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
+const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_dict_topn<group>", "k_dict_topn", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
                                             "k_scan_simple<2,rich>", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
                                             "k_merge_spans", "k_finalize", "k_facet_select", "k_locality", "k_boost1n"};
 
@@ -209,6 +209,127 @@ static size_t pack_blob(const CompiledQuery& cq, const Index& idx, uint8_t* dst,
     return off;
 }
 
+// ---- leaf top-n of a suggest batch (dict_topn.hip)
+namespace {
+// The 512 score classes (2 * distance + prefix_matches) as the HOST scores them: the device's log2 is not glibc's, so the kernel compares ranks of
+// these floats and never a score of its own.  ord = 0xFFFF - rank among the distinct values, best first; equal floats share a rank.
+struct TopnClasses {
+    float score[kTopnClasses];
+    uint16_t ord[kTopnClasses];
+};
+const TopnClasses& topn_classes() {
+    static const TopnClasses table = [] {
+        TopnClasses t;
+        std::vector<float> distinct;
+        for (uint32_t c = 0; c < kTopnClasses; ++c) distinct.push_back(t.score[c] = default_score_for_distance_host(uint8_t(c >> 1), (c & 1u) != 0));
+        std::sort(distinct.begin(), distinct.end(), std::greater<float>());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        for (uint32_t c = 0; c < kTopnClasses; ++c)
+            t.ord[c] = uint16_t(0xFFFFu - (std::lower_bound(distinct.begin(), distinct.end(), t.score[c], std::greater<float>()) - distinct.begin()));
+        return t;
+    }();
+    return table;
+}
+
+}  // namespace
+void topn_class_ords(uint16_t* ord) { std::memcpy(ord, topn_classes().ord, sizeof topn_classes().ord); }
+namespace {
+// The scans of `todo` have appended `count` records to d_recs.  Group them by probe on the device, run k_dict_topn for the top-n probes and
+// fill their `matches` / `scores` with its buffers; `recs` receives the records of the other probes (probe = index into todo), and only
+// those and the buffers are copied back.
+void select_topn_on_device(const Index& idx, Workspace& ws, hipStream_t st, const std::vector<FuzzyProbe*>& todo, const DictMatch* d_recs, uint32_t count,
+                           std::vector<DictMatch>& recs) {
+    const uint32_t n_ranks = uint32_t(todo.size());
+    uint32_t n_full = 0;
+    for (const FuzzyProbe* fp : todo) n_full += fp->top_n == 0;
+    // the full-route probes are ranked first: their records are one contiguous piece at the front of the sorted arrays
+    std::vector<uint32_t> rank_of(n_ranks), probe_of(n_ranks), desc_probe;
+    std::vector<TopnProbeD> descs;
+    uint32_t next_full = 0, next_topn = n_full, max_top_n = 0;
+    uint64_t room = 0;  // entries of all buffers when every one fills up
+    for (uint32_t i = 0; i < n_ranks; ++i) {
+        const FuzzyProbe& fp = *todo[i];
+        rank_of[i] = fp.top_n ? next_topn++ : next_full++;
+        probe_of[rank_of[i]] = i;
+        if (!fp.top_n) continue;
+        if (fp.top_n > kTopnMax) throw VelociError(ERR_DEVICE, "internal: a top-n probe beyond the kernel's buffer");
+        descs.push_back(TopnProbeD{rank_of[i], fp.top_n, fp.lev, fp.check_prefix ? 1u : 0u, {0u, 0u, 0u, 0u}});
+        desc_probe.push_back(i);
+        room += fp.top_n + kTopnSlack;
+        max_top_n = std::max(max_top_n, fp.top_n);
+    }
+    const uint32_t n_topn = uint32_t(descs.size());
+    const TopnClasses& classes = topn_classes();
+    // tables: [rank_of][descriptors][class ord] up, [seg: 2 * n_ranks + 1][out_off: n_topn + 1][out_n: n_topn] down
+    const size_t desc_at = align_up(size_t(n_ranks) * 4, 256), ord_at = desc_at + align_up(descs.size() * sizeof(TopnProbeD), 256),
+                 seg_at = ord_at + align_up(sizeof classes.ord, 256), seg_words = 2 * size_t(n_ranks) + 1, down_words = seg_words + 2 * size_t(n_topn) + 1;
+    ws.d_topn_meta.ensure(seg_at + down_words * 4 + 16);
+    uint8_t* meta = ws.d_topn_meta.as<uint8_t>();
+    uint32_t* d_seg = reinterpret_cast<uint32_t*>(meta + seg_at);
+    const size_t keys_sorted_at = align_up(size_t(count) * 8, 256), infos_at = 2 * keys_sorted_at, infos_sorted_at = infos_at + align_up(size_t(count) * 4, 256);
+    ws.d_topn_sort.ensure(infos_sorted_at + size_t(count) * 4 + 16);
+    uint8_t* sortb = ws.d_topn_sort.as<uint8_t>();
+    unsigned long long* d_keys_sorted = reinterpret_cast<unsigned long long*>(sortb + keys_sorted_at);
+    uint32_t* d_infos_sorted = reinterpret_cast<uint32_t*>(sortb + infos_sorted_at);
+    const size_t tmp_bytes = dict_topn_sort_tmp_bytes(count, n_ranks);
+    if (tmp_bytes == size_t(-1)) throw VelociError(ERR_DEVICE, "leaf top-n: the grouping sort's storage size");
+    ws.d_topn_tmp.ensure(tmp_bytes + 16);
+    ws.d_topn_out.ensure(size_t(std::min<uint64_t>(room, count)) * 8 + 16);  // (the buffers are packed: a probe gets min(its matches, top_n + 200) entries)
+    VQ_HIP(hipMemcpyAsync(meta, rank_of.data(), rank_of.size() * 4, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(meta + desc_at, descs.data(), descs.size() * sizeof(TopnProbeD), hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(meta + ord_at, classes.ord, sizeof classes.ord, hipMemcpyHostToDevice, st));
+    {
+        LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_TOPN_GROUP, uint64_t(count) * (12 + 2 * 12), uint64_t(count) * 12, n_ranks);
+        if (!launch_dict_topn_group(st, d_recs, count, reinterpret_cast<const uint32_t*>(meta), n_ranks, n_full, reinterpret_cast<unsigned long long*>(sortb), d_keys_sorted,
+                                    reinterpret_cast<uint32_t*>(sortb + infos_at), d_infos_sorted, ws.d_topn_tmp.p, tmp_bytes, d_seg))
+            throw VelociError(ERR_DEVICE, "leaf top-n: the grouping sort could not be queued");
+    }
+    {
+        LaunchTimer timer(idx.profile.enabled, ws, st, K_DICT_TOPN, 0, 0, n_topn);
+        launch_dict_topn(st, reinterpret_cast<const TopnProbeD*>(meta + desc_at), n_topn, max_top_n, d_keys_sorted, d_infos_sorted, d_seg,
+                         reinterpret_cast<const uint16_t*>(meta + ord_at), d_seg + seg_words, d_seg + seg_words + n_topn + 1, ws.d_topn_out.as<unsigned long long>());
+    }
+    VQ_HIP(hipGetLastError());
+    std::vector<uint32_t> down(down_words);
+    VQ_HIP(hipMemcpyAsync(down.data(), d_seg, down_words * 4, hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipStreamSynchronize(st));
+    const uint32_t full_records = down[seg_words - 1];
+    const uint32_t* out_off = down.data() + seg_words;
+    const uint32_t* out_n = out_off + n_topn + 1;
+    if (full_records > count || out_off[n_topn] > count - full_records) throw VelociError(ERR_DEVICE, "leaf top-n: more records to copy back than there are");
+    std::vector<unsigned long long> bufs(out_off[n_topn]), keys(full_records);
+    std::vector<uint32_t> infos(full_records);
+    if (!bufs.empty()) VQ_HIP(hipMemcpyAsync(bufs.data(), ws.d_topn_out.p, bufs.size() * 8, hipMemcpyDeviceToHost, st));
+    if (full_records) {
+        VQ_HIP(hipMemcpyAsync(keys.data(), d_keys_sorted, size_t(full_records) * 8, hipMemcpyDeviceToHost, st));
+        VQ_HIP(hipMemcpyAsync(infos.data(), d_infos_sorted, size_t(full_records) * 4, hipMemcpyDeviceToHost, st));
+    }
+    VQ_HIP(hipStreamSynchronize(st));
+    recs.resize(full_records);
+    if (full_records) {
+        for (uint32_t r = 0; r < full_records; ++r) {
+            const uint32_t rank = uint32_t(keys[r] >> 32);
+            if (rank >= n_full) throw VelociError(ERR_DEVICE, "leaf top-n: a top-n probe's record inside the full-route piece");
+            recs[r] = DictMatch{probe_of[rank], uint32_t(keys[r]), infos[r]};
+        }
+    }
+    for (uint32_t j = 0; j < n_topn; ++j) {
+        FuzzyProbe& fp = *todo[desc_probe[j]];
+        const uint32_t n = out_n[j];
+        if (n > out_off[j + 1] - out_off[j]) throw VelociError(ERR_DEVICE, "leaf top-n: a buffer longer than its room");
+        fp.topn_copied = out_off[j + 1] - out_off[j];
+        fp.matches.resize(n);
+        fp.scores.resize(n);
+        for (uint32_t k = 0; k < n; ++k) {  // buffer order, NOT ascending ids
+            const unsigned long long e = bufs[out_off[j] + k];
+            fp.matches[k] = uint32_t(e);
+            fp.scores[k] = classes.score[(e >> 32) & (kTopnClasses - 1u)];
+        }
+        fp.answered = true;
+    }
+}
+}  // namespace
+
 // Answer every dictionary scan of a batch with k_dict_scan launches (grid.y = probe), then bring the match
 // sets back sorted ascending (== FST stream order, which is what the reference's callback order is).
 void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStream_t st) {
@@ -290,6 +411,11 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
             P.lm = 0xFFFFFFFFu;
             host_scored[i] = 1;
         }
+    }
+    bool any_topn = false;
+    for (size_t i = 0; i < todo.size(); ++i) {
+        any_topn = any_topn || todo[i]->top_n != 0;
+        if (todo[i]->top_n && (todo[i]->regex || host_scored[i])) throw VelociError(ERR_DEVICE, "internal: a top-n probe whose hits the device does not score");
     }
     DevBuf &d_probes = ws.d_probe_desc, &d_count = ws.d_probe_counts, &d_out = ws.d_probe_ids;
     // one descriptor buffer: [DictProbe x N][DictProbeW x N][pool]
@@ -385,6 +511,10 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
         if (std::getenv("VQ_TIMING")) {
             std::fprintf(stderr, "[vq timing] dictionary scan: %zu probes, %u matches\n", todo.size(), count);
         }
+        if (any_topn) {  // suggest batch: only the full-route probes' records and the top-n buffers come back
+            select_topn_on_device(idx, ws, st, todo, d_out.as<DictMatch>(), count, recs);
+            break;
+        }
         recs.resize(count);
         if (count) {
             VQ_HIP(hipMemcpyAsync(recs.data(), d_out.p, size_t(count) * sizeof(DictMatch), hipMemcpyDeviceToHost, st));
@@ -406,6 +536,7 @@ void run_fuzzy_probes(const Index& idx, Workspace& ws, FuzzyTable& table, hipStr
     size_t r = 0;
     for (size_t i = 0; i < todo.size(); ++i) {
         FuzzyProbe& fp = *todo[i];
+        if (fp.top_n) continue;  // (filled by select_topn_on_device; no record of `recs` is its)
         fp.matches.clear();
         fp.scores.clear();
         fp.answered = true;
@@ -1712,6 +1843,23 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     return pb;
 }
 
+// One finished batch into the profile: the device time of every timed launch of the workspace under its kernel's entry (the caller holds
+// profile_mutex, and the launches' stream has been synchronised)
+static void account_timed_launches(Profile& P, Workspace& ws) {
+    P.batches += 1;
+    for (const TimedLaunch& t : ws.timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ws.ev_pool[t.ev_begin], ws.ev_pool[t.ev_end]) != hipSuccess) continue;
+        KernelProfile& k = P.k[t.kernel];
+        k.ms += ms;
+        k.launches += 1;
+        k.layout_bytes += t.layout_bytes;
+        k.algorithmic_bytes += t.algorithmic_bytes;
+        k.queries += t.queries;
+    }
+    ws.timed.clear();
+}
+
 // The dictionary scans of a suggest / highlight request, answered: on the next workspace in turn, on the pre-passes' stream
 static FuzzyTable run_suggest_probes(const Index& idx, const vqreq::Request& req) {
     FuzzyTable fuzzy;
@@ -1726,13 +1874,11 @@ static FuzzyTable run_suggest_probes(const Index& idx, const vqreq::Request& req
 }
 
 // suggest_multi (search_field.rs:194-219): dictionary side only — the parts' matched terms, equal texts merged keeping the best score, ranked
-std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& req) {
-    if (!req.suggest) throw VelociError(ERR_INVALID_REQUEST, "only suggest allowed in suggest function");
-    VQ_HIP(hipSetDevice(idx.device));
-    const FuzzyTable fuzzy = run_suggest_probes(idx, req);
+// (the merge over the parts, shared by the single request and the batch: `fuzzy` holds the answered scans of the request's parts)
+static std::vector<SuggestEntry> merge_suggest_parts(const Index& idx, const vqreq::Request& req, const FuzzyTable& fuzzy, bool topn_probes = false) {
     std::vector<SuggestEntry> out;
     for (auto& part : *req.suggest) {
-        auto one = suggest_part(idx, part, fuzzy.empty() ? nullptr : &fuzzy);
+        auto one = suggest_part(idx, part, fuzzy.empty() ? nullptr : &fuzzy, topn_probes);
         out.insert(out.end(), one.begin(), one.end());
     }
     std::stable_sort(out.begin(), out.end(), [](const SuggestEntry& a, const SuggestEntry& b) { return a.text > b.text; });  // :176 (descending)
@@ -1747,6 +1893,62 @@ std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& re
     merged.erase(merged.begin(), merged.begin() + skip);
     if (req.top && merged.size() > *req.top) merged.resize(*req.top);
     return merged;
+}
+std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& req) {
+    if (!req.suggest) throw VelociError(ERR_INVALID_REQUEST, "only suggest allowed in suggest function");
+    VQ_HIP(hipSetDevice(idx.device));
+    const FuzzyTable fuzzy = run_suggest_probes(idx, req);
+    return merge_suggest_parts(idx, req, fuzzy);
+}
+
+// n suggest requests as one batch: the probes of ALL requests in one table (equal probes are scanned once), one run of the probe runner, then
+// every request finished by the single request's own code.  A part with its own top gets a top-n probe where it qualifies (probe_part).
+void run_suggest_batch(const Index& idx, const vqreq::Request* const* reqs, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
+                       std::vector<std::string>& errors) {
+    out.assign(n, {});
+    status.assign(n, 0);
+    errors.assign(n, std::string());
+    if (!n) return;
+    VQ_HIP(hipSetDevice(idx.device));
+    FuzzyTable fuzzy;
+    for (size_t i = 0; i < n; ++i) {
+        if (!reqs[i]) {
+            status[i] = vqreq::ERR_INVALID_ARGUMENT;
+            errors[i] = "null request";
+        } else if (!reqs[i]->suggest) {
+            status[i] = ERR_INVALID_REQUEST;
+            errors[i] = "only suggest allowed in suggest function";
+        } else collect_suggest_batch_probes(idx, *reqs[i], fuzzy);
+    }
+    if (!fuzzy.empty()) {
+        Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
+        std::unique_lock<std::mutex> lock(ws.mu);
+        ws.timed.clear();
+        ws.ev_used = 0;
+        run_fuzzy_probes(idx, ws, fuzzy, idx.pre_stream ? idx.pre_stream : idx.stream);
+        if (idx.profile.enabled) {  // (every launch of the runner is behind a host synchronisation)
+            std::lock_guard<std::mutex> g(idx.profile_mutex);
+            account_timed_launches(idx.profile, ws);
+        }
+        uint64_t topn = 0, records = 0;
+        for (auto& kv : fuzzy) {
+            if (kv.second.status != 0) continue;
+            topn += kv.second.top_n != 0;
+            records += kv.second.top_n ? kv.second.topn_copied : kv.second.matches.size();
+        }
+        idx.suggest_topn_probes.fetch_add(topn, std::memory_order_relaxed);
+        idx.suggest_records_back.fetch_add(records, std::memory_order_relaxed);
+    }
+    parallel_for(n, std::min(host_threads(), n), [&](size_t i) {
+        if (status[i] != 0) return;
+        try {
+            out[i] = merge_suggest_parts(idx, *reqs[i], fuzzy, true);
+        } catch (const VelociError& e) {
+            status[i] = e.code;
+            errors[i] = e.what();
+            out[i].clear();
+        }
+    });
 }
 
 // search_field::highlight (search_field.rs:233-245): the part's terms normalised (util.rs:11-29), its dictionary scan on the device, the snippets on
@@ -2136,22 +2338,11 @@ void finish_batch(const Index& idx, PartialBatch& pb, const void* gathered_devic
         if (prof) {
             std::lock_guard<std::mutex> g(idx.profile_mutex);
             Profile& P = idx.profile;
-            P.batches += 1;
-            for (const TimedLaunch& t : ws.timed) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ws.ev_pool[t.ev_begin], ws.ev_pool[t.ev_end]) != hipSuccess) continue;
-                KernelProfile& k = P.k[t.kernel];
-                k.ms += ms;
-                k.launches += 1;
-                k.layout_bytes += t.layout_bytes;
-                k.algorithmic_bytes += t.algorithmic_bytes;
-                k.queries += t.queries;
-            }
+            account_timed_launches(P, ws);
             for (uint32_t q = 0; q < nq && q < pb.qclass.size(); ++q) {
                 P.k[pb.qclass[q]].layout_bytes += gathered_bytes[q];
                 P.k[pb.qclass[q]].gathered_bytes += gathered_bytes[q];
             }
-            ws.timed.clear();
         }
     }
     const uint64_t ns = uint64_t(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pb.t0).count());

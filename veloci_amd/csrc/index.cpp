@@ -181,6 +181,7 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
             std::vector<uint32_t> raw, low;
             std::vector<uint64_t> seen(0x110000 / 64, 0ull);  // the dictionary's alphabet (regex leaves), collected on the way
             for (uint32_t i = 0; i < d.terms.size(); ++i) {
+                d.max_term_bytes = std::max(d.max_term_bytes, d.terms[i].size());
                 for (uint32_t cp : vqtext::decode_utf8(d.terms[i])) {
                     if (cp < 0x110000u) seen[cp >> 6] |= 1ull << (cp & 63u);
                     else d.alphabet.push_back(cp);

@@ -125,6 +125,30 @@ void launch_dict_regex(hipStream_t st, uint32_t char_bytes, bool small_tables, c
                        uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const void* chars, uint32_t num_terms, uint32_t* out_count, uint32_t out_cap,
                        DictMatch* out);
 
+// ---- leaf top-n of the batched suggest (dict_topn.hip): the scans' matches grouped by probe on the device, then the reference's top-n loop per probe
+struct TopnProbeD {  // one top-n probe of k_dict_topn
+    uint32_t rank;          // its segment of the sorted keys: seg[2 * rank], seg[2 * rank + 1]
+    uint32_t top_n;         // top + skip (1 .. kTopnMax): the buffer holds at most top_n + 200 entries
+    uint32_t lev;           // the clamped distance of the scoring automaton (search_field.rs:285-287)
+    uint32_t check_prefix;  // 1: a hit that starts with the term gets the prefix score (:302)
+    uint32_t pad[4];
+};
+constexpr uint32_t kTopnSlack = 200;                   // sort.rs:26
+constexpr uint32_t kTopnMax = 2048 - kTopnSlack;       // the kernel's LDS buffer: 2048 entries of 8 bytes
+constexpr uint32_t kTopnClasses = 512;                 // 2 * distance (u8) + prefix_matches
+size_t dict_topn_sort_tmp_bytes(uint32_t n, uint32_t n_ranks);  // temporary storage of the grouping sort, size_t(-1) on an error
+// recs[0, n) -> keys rank_of[probe] << 32 | term with `info` as value, sorted ascending into keys_sorted / infos_sorted; seg (2 * n_ranks + 1 words):
+// every rank's [begin, end) in the sorted arrays, then the records of the ranks below n_full.  false: the sort could not be queued
+bool launch_dict_topn_group(hipStream_t st, const DictMatch* recs, uint32_t n, const uint32_t* rank_of, uint32_t n_ranks, uint32_t n_full, unsigned long long* keys_in,
+                            unsigned long long* keys_sorted, uint32_t* infos_in, uint32_t* infos_sorted, void* tmp, size_t tmp_bytes, uint32_t* seg);
+// one wave per probe; class_ord[kTopnClasses]: 0xFFFF - rank of the class's score among the distinct scores.  The buffers are packed: probe p gets
+// min(its matches, top_n + 200) entries of `out` from out_off[p] on (out_off: n_probes + 1 words, the last the total, never more than the
+// records there are) and writes out_n[p] entries (class << 32 | term) there
+void launch_dict_topn(hipStream_t st, const TopnProbeD* probes, uint32_t n_probes, uint32_t max_top_n, const unsigned long long* keys, const uint32_t* infos,
+                      const uint32_t* seg, const uint16_t* class_ord, uint32_t* out_off, uint32_t* out_n, unsigned long long* out);
+int debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t n, uint32_t top_n, const uint16_t* class_ord_host, uint32_t* out_terms, uint32_t* out_classes,
+                    uint32_t* out_n);
+
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst
     uint64_t src, dst;

@@ -216,6 +216,39 @@ def highlight_text(text, terms, snippet_info=None, tokenized=True):
         cap = n
 
 
+def suggest_batch(requests, index, raise_on_error=True):
+    """n independent suggest requests (each as `suggest` takes it) answered as one device batch (`vq_suggest_batch`).
+    -> one [(text, score, term_id)] per request; a failing request raises, or with raise_on_error=False yields its VelociError."""
+    L = _lib.lib()
+    texts = []
+    for r in requests:
+        if isinstance(r, dict):
+            r = json.dumps(r)
+        texts.append(r.encode() if isinstance(r, str) else r)
+    n = len(texts)
+    arr = (C.c_char_p * n)(*texts)
+    lens = (C.c_size_t * n)(*[len(t) for t in texts])
+    outs = (C.c_void_p * n)()
+    status = (C.c_int * n)()
+    _lib.check(L.vq_suggest_batch(index.h, arr, lens, n, outs, status))
+    first_error = L.vq_last_error().decode("utf-8", "replace")
+    results = []
+    try:
+        for i in range(n):
+            if status[i] != 0:
+                if raise_on_error:
+                    raise VelociError(status[i], first_error)
+                results.append(VelociError(status[i], _lib.ERR_NAMES.get(status[i], "error")))
+                continue
+            out = C.c_void_p(outs[i])
+            results.append([(L.vq_suggest_text(out, k).decode(), float(L.vq_suggest_score(out, k)), int(L.vq_suggest_term_id(out, k))) for k in range(L.vq_suggest_len(out))])
+    finally:
+        for i in range(n):
+            if outs[i]:
+                L.vq_suggest_free(C.c_void_p(outs[i]))
+    return results
+
+
 def search_batch(requests, index, raise_on_error=True):
     """n independent searches executed as one device batch (`vq_search_batch`)."""
     L = _lib.lib()

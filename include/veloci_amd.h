@@ -242,6 +242,15 @@ int vq_suggest_batch(const vq_index*, const char* const* json, const size_t* len
  * vq_suggest_score, vq_suggest_term_id = the text id.  Where the reference panics (a hit without a snippet: an untokenised field, "snippet" not
  * set) the call returns VQ_ERR_INVALID_REQUEST.  Needs the field's tokens_to_text_id and text_id_to_token_ids stores. */
 int vq_highlight_json(const vq_index*, const char* json, size_t len, vq_suggest_result** out);
+/* n independent highlight parts (each text as vq_highlight_json takes it) answered as one device batch.  out[i] receives part i's result, or
+ * NULL with status[i] != VQ_OK; the text of the first failing part is in vq_last_error.  Returns VQ_OK when the batch ran.  Every out[i] equals
+ * what vq_highlight_json returns for json[i].  The dictionary scans of all parts run together (equal probes once).  A part with "snippet": true
+ * and its own `top` (1 <= top + skip <= 1024) on a tokenized field, whose token scores are all finite and above 0, has its texts ranked on the
+ * device: the best matched-token score per text (k_text_best) and the page's top + skip texts by (score descending, text id ascending)
+ * (k_text_select) — only those texts get a snippet.  That needs the field's tokens_to_text_id and text_id_to_token_ids to hold the same
+ * (token, text) pairs, checked once per field on first use (a tokens_to_text_id table the index build did not stage goes to HBM then); any other
+ * part is answered inside the batch by vq_highlight_json's own code.  VQ_NO_HIGHLIGHT_RANK=1 keeps every part on that route. */
+int vq_highlight_batch(const vq_index*, const char* const* json, const size_t* len, size_t n, vq_suggest_result** out, int* status);
 /* == highlight_field::highlight_text(text, set, opt, tokenizer) (src/highlight_field.rs:92-146): `text` with the tokens that are in `terms` wrapped in
  * the snippet tags, cut into windows like vq_highlight_json's snippets — what why_found highlighting (highlight_on_original_document, :148-185) applies to
  * every text of a returned document with the field's terms from vq_result_why_found_terms_json.  `tokenized` = the field has a tokenizer (the default
@@ -382,6 +391,17 @@ void vq_index_suggest_topn_probes(const vq_index*, uint64_t* topn_probes, uint64
  * 2 * distance + prefix_matches (< 512), top_n in 1 .. 1848.  Writes the loop's final buffer in buffer order (the out arrays take top_n + 200
  * entries) and its length.  0; -1 without a device; -2 for arguments outside these ranges. */
 int vq_debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t n, uint32_t top_n, uint32_t* out_terms, uint32_t* out_classes, uint32_t* out_n);
+
+/* Totals of this index's vq_highlight_batch calls since it was built: parts whose texts were ranked and cut to the page on the device
+ * (k_text_best / k_text_select), and snippets the batch entry point built on the host (a device part builds one per returned text, a part on
+ * the host route one per text that holds a matched token).  Either pointer may be NULL. */
+void vq_index_highlight_rank_counts(const vq_index*, uint64_t* device_parts, uint64_t* snippets_built);
+/* k_text_best + k_text_select on a caller's CSR: row r = row_vals[row_off[r] .. row_off[r + 1]) holds text ids below num_texts and carries the
+ * f32 score bits row_score_bits[r] (finite, > 0); top_n in 1 .. 1024.  Writes the top_n texts by (best score descending, text id ascending) —
+ * the out arrays take top_n entries —, their number and the number of texts that occur in any row.  0; -1 without a device; -2 for arguments
+ * outside these ranges. */
+int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const uint32_t* row_score_bits, uint32_t num_rows, uint32_t num_texts, uint32_t top_n,
+                       uint32_t* out_texts, uint32_t* out_score_bits, uint32_t* out_n, uint32_t* out_touched);
 
 /* The facet selection kernels (k_facet_select / k_facet_select_wide: facet.rs:19-23, count descending; ties by value id ascending) on a
  * caller's histogram of `num_values` counts, placed `misalign` (0-3) counters behind a 16-byte boundary as inside a batch's histogram area:

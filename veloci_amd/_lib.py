@@ -17,12 +17,12 @@ SYMBOLS = [
     "vq_index_free", "vq_index_set_stream", "vq_index_set_streams", "vq_index_set_allreduce", "vq_index_device_bytes", "vq_request_parse", "vq_request_free", "vq_request_to_json", "vq_request_has_facets", "vq_request_page_after", "vq_result_is_page", "vq_debug_to_lowercase", "vq_debug_normalize_text", "vq_debug_sort_unique_u32", "vq_debug_compile", "vq_debug_regex_compile", "vq_result_num_hits",
     "vq_result_execution_time_ns", "vq_result_len", "vq_result_ids", "vq_result_scores", "vq_result_num_facets", "vq_result_facet_field",
     "vq_result_facet_len", "vq_result_facet_value", "vq_result_facet_count", "vq_result_to_json", "vq_result_why_found_terms_json", "vq_result_why_found_info_json", "vq_result_explain_json", "vq_result_free", "vq_search", "vq_search_json",
-    "vq_highlight_json", "vq_highlight_text", "vq_suggest_json", "vq_suggest_len", "vq_suggest_text", "vq_suggest_score", "vq_suggest_term_id", "vq_suggest_free", "vq_suggest_batch",
+    "vq_highlight_json", "vq_highlight_text", "vq_suggest_json", "vq_suggest_len", "vq_suggest_text", "vq_suggest_score", "vq_suggest_term_id", "vq_suggest_free", "vq_suggest_batch", "vq_highlight_batch",
     "vq_search_batch", "vq_search_batch_flat", "vq_search_batch_partial", "vq_partial_bytes", "vq_partial_device_ptr", "vq_partial_hist_bytes",
     "vq_partial_hist_device_ptr", "vq_merge_partials", "vq_merge_partials_flat", "vq_partial_free",
     "vq_search_batch_partial_at", "vq_partial_slots", "vq_index_partial_arena_ptr", "vq_partial_total_bytes", "vq_merge_partials_flat_strided",
     "vq_comm_unique_id", "vq_comm_init", "vq_comm_init_custom", "vq_comm_destroy", "vq_shard_step_begin", "vq_shard_step_end", "vq_shard_step_free", "vq_shard_step_flat",
-    "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_version",
+    "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_version",
 ]
 COMM_ID_BYTES = 128
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -110,6 +110,7 @@ def lib():
         "vq_suggest_term_id": (u32, [vp, sz]),
         "vq_suggest_free": (None, [vp]),
         "vq_suggest_batch": (i, [vp, C.POINTER(cp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(i)]),
+        "vq_highlight_batch": (i, [vp, C.POINTER(cp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(i)]),
         "vq_result_free": (None, [vp]),
         "vq_search": (i, [vp, vp, C.POINTER(vp)]),
         "vq_search_json": (i, [vp, cp, sz, C.POINTER(vp)]),
@@ -126,6 +127,8 @@ def lib():
         "vq_index_speculative_reruns": (u64, [vp]),
         "vq_index_suggest_topn_probes": (None, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vq_debug_dict_topn": (i, [vp, vp, u32, u32, vp, vp, C.POINTER(u32)]),
+        "vq_index_highlight_rank_counts": (None, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "vq_debug_text_rank": (i, [vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(u32)]),
         "vq_merge_partials": (i, [vp, vp, vp, u32, C.POINTER(vp), C.POINTER(i)]),
         "vq_merge_partials_flat": (i, [vp, vp, vp, u32, sz, vp, vp, vp, vp, vp]),
         "vq_partial_free": (None, [vp]),

@@ -237,7 +237,7 @@ void dump_parts(std::string& s, const std::optional<std::vector<vqreq::RequestSe
 extern "C" {
 
 const char* vq_last_error(void) { return g_err.c_str(); }
-const char* vq_version(void) { return "veloci_amd 0.4 (gfx950)"; }
+const char* vq_version(void) { return "veloci_amd 0.5 (gfx950)"; }
 /* self-check (tests): inputs for which the kernels' fast a/100 differs from the correctly rounded division, over all f16 values */
 uint32_t vq_debug_div100_mismatches(void) { return vq::debug_div100_mismatches(); }
 /* tools/probe_occupancy.py (like the stamp readers below: exported, not part of the header): LDS bytes of a probe kernel's one-wave workgroup (shape: kProbe* of kernels.hpp; nd / na operands beside the cover / probed as arrays; arr_slot words per
@@ -264,6 +264,37 @@ int vq_debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t 
     uint16_t ord[vq::kTopnClasses];
     vq::topn_class_ords(ord);
     return vq::debug_dict_topn(terms, classes, n, top_n, ord, out_terms, out_classes, out_n);
+}
+/* tests, tools: since the index was built, the parts of highlight batches whose texts were ranked on the device and the snippets those batches built */
+void vq_index_highlight_rank_counts(const vq_index* index, uint64_t* device_parts, uint64_t* snippets_built) {
+    if (device_parts) *device_parts = index ? index->idx->highlight_device_parts.load() : 0;
+    if (snippets_built) *snippets_built = index ? index->idx->highlight_snippets_built.load() : 0;
+}
+/* self-check (tests): k_text_best + k_text_select on a caller's CSR -> the top_n texts by (score bits descending, text id ascending) and the number
+   of touched texts.  0; -1 without a device; -2 for arguments the kernels do not take */
+int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const uint32_t* row_score_bits, uint32_t num_rows, uint32_t num_texts, uint32_t top_n,
+                       uint32_t* out_texts, uint32_t* out_score_bits, uint32_t* out_n, uint32_t* out_touched) {
+    if (!row_off || (num_rows && !row_score_bits) || !out_texts || !out_score_bits || !out_n || !out_touched) return -2;
+    if (top_n == 0 || top_n > vq::kTextRankMaxTop || num_texts == 0 || uint64_t(num_texts) * 4 > vq::kTextRankBudget || row_off[0] != 0) return -2;
+    for (uint32_t r = 0; r < num_rows; ++r) {
+        if (row_off[r + 1] < row_off[r] || row_score_bits[r] == 0 || row_score_bits[r] >= 0x7F800000u) return -2;  // (finite and > 0)
+    }
+    const uint64_t n_vals = row_off[num_rows];
+    if ((n_vals && !row_vals) || n_vals > (uint64_t(1) << 31)) return -2;
+    for (uint64_t k = 0; k < n_vals; ++k)
+        if (row_vals[k] >= num_texts) return -2;
+    try {
+        std::vector<std::pair<uint32_t, uint32_t>> picked;
+        vq::debug_text_rank(row_off, row_vals, row_score_bits, num_rows, num_texts, top_n, picked, out_touched);
+        for (size_t k = 0; k < picked.size(); ++k) {
+            out_texts[k] = picked[k].first;
+            out_score_bits[k] = picked[k].second;
+        }
+        *out_n = uint32_t(picked.size());
+    } catch (const std::exception&) {
+        return -1;
+    }
+    return 0;
 }
 /* self-check (tests): the facet top-`top` kernels on a caller's histogram */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts) {
@@ -709,6 +740,46 @@ int vq_highlight_json(const vq_index* index, const char* json, size_t len, vq_su
         }
         *out = r;
     });
+}
+int vq_highlight_batch(const vq_index* index, const char* const* json, const size_t* len, size_t n, vq_suggest_result** out, int* status) {
+    std::string first_error;
+    const int rc = guard([&] {
+        if (!index || (n && (!json || !len || !out))) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_highlight_batch: null argument");
+        for (size_t i = 0; i < n; ++i) out[i] = nullptr;
+        std::vector<vqreq::RequestSearchPart> parsed(n);
+        std::vector<const vqreq::RequestSearchPart*> parts(n, nullptr);
+        std::vector<int> parse_status(n, 0);
+        std::vector<std::string> parse_error(n);
+        for (size_t i = 0; i < n; ++i) {
+            try {
+                if (!json[i]) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_highlight_batch: null request text");
+                try {
+                    parsed[i] = vqreq::search_part_from_json(vqjson::parse(json[i], len[i]));
+                } catch (const vqjson::ParseError& e) {
+                    throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+                }
+                parts[i] = &parsed[i];
+            } catch (const VelociError& e) {
+                parse_status[i] = e.code;
+                parse_error[i] = e.what();
+            }
+        }
+        std::vector<std::vector<SuggestEntry>> results;
+        std::vector<int> st;
+        std::vector<std::string> errs;
+        run_highlight_batch(*index->idx, parts.data(), n, results, st, errs);
+        for (size_t i = 0; i < n; ++i) {
+            const int code = parse_status[i] ? parse_status[i] : st[i];
+            if (status) status[i] = code;
+            if (code == 0) {
+                auto* r = new vq_suggest_result();
+                r->e = std::move(results[i]);
+                out[i] = r;
+            } else if (first_error.empty()) first_error = parse_status[i] ? parse_error[i] : errs[i];
+        }
+    });
+    if (rc == VQ_OK && !first_error.empty()) g_err = first_error;  // (the batch ran: the first failing part's text)
+    return rc;
 }
 // highlight_text (highlight_field.rs:92-146).  Returns the snippet's byte length (written to `out` when it fits `cap`), VQ_HIGHLIGHT_NONE when there is
 // nothing to highlight, VQ_HIGHLIGHT_ERROR on an error (vq_last_error); a length above `cap` means: call again with a larger buffer.

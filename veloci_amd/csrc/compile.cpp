@@ -2626,10 +2626,9 @@ std::optional<std::string> highlight_text(const std::string& text, const std::ve
     return out;
 }
 
-std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
-    static const vqreq::SnippetInfo kDefault;
-    const vqreq::SnippetInfo& opt = part.has_snippet_info ? part.snippet_info : kDefault;
-    check_snippet_window(opt);
+static const vqreq::SnippetInfo kDefaultSnippetInfo;
+HighlightLookup highlight_lookup(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
+    check_snippet_window(part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo);
     RequestSearchPart lookup = part;  // get_term_ids_in_field does not look at the snippet fields
     lookup.snippet.reset();
     lookup.has_snippet_info = false;
@@ -2640,7 +2639,32 @@ std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPa
     l.get_scores = true;
     c.lookup_terms(idx, l, true, false);
     if (lookup.token_value) c.apply_token_value(*lookup.token_value, l);
+    HighlightLookup lk;
+    lk.path = l.path;
+    lk.hits_scores = std::move(l.hits_scores);
+    auto cit = idx.columns.find(lk.path.substr(0, lk.path.size() - std::strlen(TEXTINDEX)));
+    lk.tokenized = cit != idx.columns.end() && cit->second.tokenize;
+    lk.add_snippets = part.snippet.value_or(false);
+    return lk;
+}
 
+bool highlight_snippet(const Index& idx, const HighlightLookup& lk, const RequestSearchPart& part, uint32_t text, const std::vector<uint32_t>& wanted_sorted, std::string* out) {
+    const vqreq::SnippetInfo& opt = part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo;
+    auto tit = idx.kv.find(lk.path + ".text_id_to_token_ids");
+    if (tit == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + lk.path + ".text_id_to_token_ids");
+    const uint32_t *b, *e;
+    if (!tit->second.host_row(text, &b, &e)) return false;
+    bool any = false;
+    *out = snippet_of_text(idx.dict.at(lk.path), b, size_t(e - b), wanted_sorted, opt, &any);
+    return any;
+}
+
+std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
+    return highlight_resolve(idx, part, highlight_lookup(idx, part, fuzzy));
+}
+
+std::vector<SuggestEntry> highlight_resolve(const Index& idx, const RequestSearchPart& part, const HighlightLookup& l) {
+    const vqreq::SnippetInfo& opt = part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo;
     struct TextHit {
         uint32_t text;
         float score;
@@ -2649,9 +2673,8 @@ std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPa
     std::vector<TextHit> hits;
     std::vector<std::pair<uint32_t, float>> ranked;  // (text id, best score): SearchFieldResult::hits_scores after the resolve step
     const std::string& path = l.path;
-    auto cit = idx.columns.find(path.substr(0, path.size() - std::strlen(TEXTINDEX)));
-    const bool tokenized = cit != idx.columns.end() && cit->second.tokenize;
-    const bool add_snippets = part.snippet.value_or(false);
+    const bool tokenized = l.tokenized;
+    const bool add_snippets = l.add_snippets;
     std::map<uint32_t, std::string> snippets;
     for (auto& h : l.hits_scores) ranked.push_back(h);
     if (tokenized) {

@@ -225,9 +225,28 @@ void topn_class_ords(uint16_t* ord);  // k_dict_topn's class table (kTopnClasses
 bool probe_scored_on_device(const Index& idx, const FuzzyProbe& fp);  // run_fuzzy_probes' rule: the scan kernel scores the hits of this probe
 std::optional<std::string> highlight_text(const std::string& text, const std::vector<std::string>& terms, const vqreq::SnippetInfo& opt, bool tokenized);  // highlight_field.rs:92-146
 vqreq::Request page_request_after(const vqreq::Request& request, float score, uint32_t id);
+// highlight_part in its two steps (the batched highlight runs them apart): the part's matched tokens with their scores (get_term_ids_in_field +
+// token_value), then resolve_token_hits_to_text_id with snippets over the host stores
+struct HighlightLookup {
+    std::string path;                                      // "<field>.textindex"
+    std::vector<std::pair<uint32_t, float>> hits_scores;   // (token id, score)
+    bool tokenized = false, add_snippets = false;
+};
+HighlightLookup highlight_lookup(const Index& idx, const vqreq::RequestSearchPart& part, const FuzzyTable* fuzzy);
+std::vector<SuggestEntry> highlight_resolve(const Index& idx, const vqreq::RequestSearchPart& part, const HighlightLookup& lk);
 std::vector<SuggestEntry> highlight_part(const Index& idx, const vqreq::RequestSearchPart& part, const FuzzyTable* fuzzy);
+// the snippet of `text` of field `lk.path` for the matched tokens `wanted_sorted` (highlight_document, highlight_field.rs:187-272); false: none
+bool highlight_snippet(const Index& idx, const HighlightLookup& lk, const vqreq::RequestSearchPart& part, uint32_t text, const std::vector<uint32_t>& wanted_sorted, std::string* out);
 std::vector<SuggestEntry> run_highlight(const Index& idx, vqreq::RequestSearchPart part);  // search_field::highlight, search_field.rs:233-245
 std::vector<SuggestEntry> run_suggest(const Index& idx, const vqreq::Request& req);  // suggest_multi, search_field.rs:194-219
+// n highlight parts as one device batch (a null part fails alone); every result equals run_highlight's.  A part that qualifies has
+// its texts ranked and cut to the page on the device (text_rank.hip) and only the page's snippets built
+void run_highlight_batch(const Index& idx, const vqreq::RequestSearchPart* const* parts, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
+                         std::vector<std::string>& errors);
+// k_text_best + k_text_select alone on a caller's CSR (vq_debug_text_rank): rows [row_off[r], row_off[r + 1]) of `vals` with score bits[r] -> the
+// top_n texts sorted by (bits descending, text ascending) and the number of touched texts.  Throws without a device
+void debug_text_rank(const uint64_t* row_off, const uint32_t* vals, const uint32_t* bits, uint32_t num_rows, uint32_t num_texts, uint32_t top_n,
+                     std::vector<std::pair<uint32_t, uint32_t>>& picked, uint32_t* touched);
 // n suggest requests as one device batch (a null request, or one that fails, fails alone: status / errors); every result equals run_suggest's
 void run_suggest_batch(const Index& idx, const vqreq::Request* const* reqs, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
                        std::vector<std::string>& errors);
@@ -445,7 +464,7 @@ constexpr int kWorkspaces = 4;  // batches in flight per index (host compile of 
 
 // Kernels the profiler accounts separately (vq_profile_json): the pre-passes, one entry per scan class, the merges.
 enum KernelId : int {
-    K_DICT_SCAN = 0, K_DICT_REGEX, K_DICT_TOPN_GROUP, K_DICT_TOPN, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
+    K_DICT_SCAN = 0, K_DICT_REGEX, K_DICT_TOPN_GROUP, K_DICT_TOPN, K_TEXT_BEST, K_TEXT_SELECT, K_UNION_COUNT, K_UNION_WRITE, K_UNION_DENSE_SCATTER, K_UNION_DENSE_COUNT, K_UNION_DENSE_WRITE, K_RANGE_HITS, K_COUNT_PREPASS, K_SCAN_LEAF_F32, K_SCAN_RICH, K_SCAN_PROBE, K_SCAN_AND, K_SCAN_SIMPLE, K_SCAN_UNION,
     K_SCAN_WIDE, K_TILE_SCAN, K_MERGE_SPANS, K_FINALIZE, K_FACET_SELECT, K_LOCALITY, K_BOOST1N, K_COUNT_
 };
 extern const char* const kKernelNames[K_COUNT_];
@@ -475,6 +494,7 @@ struct Workspace {  // scratch of one in-flight batch
     DevBuf d_probe_desc, d_probe_counts, d_probe_ids;                    // dictionary scans (k_dict_scan): kept, so that no hipFree synchronises the device mid-pipeline
     DevBuf d_regex_tabs;                                                 // regex probes (k_dict_regex): descriptors + table pool
     DevBuf d_topn_sort, d_topn_tmp, d_topn_meta, d_topn_out;             // leaf top-n of a suggest batch (dict_topn.hip): keys + infos (unsorted, sorted), rocPRIM's storage, tables, buffers
+    DevBuf d_trank_best, d_trank_meta;                                   // text ranking of a highlight batch (text_rank.hip): the round's `best` arrays; descriptors, top_n table, counts + pairs
 };
 
 struct KernelProfile {
@@ -538,6 +558,20 @@ struct Index {
         if (!sharded() || v.empty()) return;
         if (!allreduce_fn || allreduce_fn(allreduce_ctx, v.data(), v.size()) != 0) throw vqreq::VelociError(vqreq::ERR_DEVICE, "all-reduce over the shards failed");
     }
+    // batched highlight: per field ("<field>.textindex") whether tokens_to_text_id and text_id_to_token_ids describe one relation (checked on first
+    // use), and the staged values of tokens_to_text_id (uploaded then, for a field whose table the index build did not stage)
+    struct HighlightField {
+        std::once_flag once;
+        bool ok = false;
+        uint32_t num_texts = 0;          // largest text id of the table + 1
+        const KVStore* t2t = nullptr;    // tokens_to_text_id
+        const KVStore* tokens = nullptr; // text_id_to_token_ids
+        const uint32_t* d_vals = nullptr;
+        DevBuf own_vals;
+    };
+    mutable std::mutex highlight_mu;
+    mutable std::map<std::string, std::unique_ptr<HighlightField>> highlight_fields;
+    mutable std::atomic<uint64_t> highlight_device_parts{0}, highlight_snippets_built{0};  // highlight batches: parts ranked on the device; snippets built (tests, tools)
     mutable std::atomic<uint64_t> suggest_topn_probes{0}, suggest_records_back{0};  // suggest batches: probes answered by k_dict_topn; match records copied back (tests, tools)
     mutable std::atomic<uint64_t> or_reruns{0};  // requests that ran a second time because k_scan_probe_or's short cut could not be confirmed (tests, tools)
     mutable std::unique_ptr<HostPool> pool;  // created on first use

@@ -39,7 +39,7 @@ static bool timing_enabled() {
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_dict_topn<group>", "k_dict_topn", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
+const char* const kKernelNames[K_COUNT_] = {"k_dict_scan", "k_dict_regex", "k_dict_topn<group>", "k_dict_topn", "k_text_best", "k_text_select", "k_union<count>", "k_union<write>", "k_union_dense_scatter", "k_union_dense_count", "k_union_dense_write", "k_range_hits", "k_tile_scan<count pre-pass>", "k_scan_leaf_f32",
                                             "k_scan_simple<2,rich>", "k_scan_probe (AND / OR)", "k_scan_simple<2> (AND)", "k_scan_simple<2>", "k_scan_union", "k_scan_wide", "k_tile_scan",
                                             "k_merge_spans", "k_finalize", "k_facet_select", "k_locality", "k_boost1n"};
 
@@ -1953,6 +1953,12 @@ void run_suggest_batch(const Index& idx, const vqreq::Request* const* reqs, size
 
 // search_field::highlight (search_field.rs:233-245): the part's terms normalised (util.rs:11-29), its dictionary scan on the device, the snippets on
 // the host, ranked by score with the part's own top / skip
+static void rank_and_cut_highlight(std::vector<SuggestEntry>& out, const vqreq::RequestSearchPart& part) {
+    std::stable_sort(out.begin(), out.end(), [](const SuggestEntry& a, const SuggestEntry& b) { return a.score > b.score; });  // :189
+    const size_t skip = std::min(part.skip.value_or(0), out.size());  // apply_top_skip, search.rs:230-239
+    out.erase(out.begin(), out.begin() + skip);
+    if (part.top && out.size() > *part.top) out.resize(*part.top);
+}
 std::vector<SuggestEntry> run_highlight(const Index& idx, vqreq::RequestSearchPart part) {
     for (auto& t : part.terms) t = vqtext::normalize_text(t);
     VQ_HIP(hipSetDevice(idx.device));
@@ -1960,11 +1966,282 @@ std::vector<SuggestEntry> run_highlight(const Index& idx, vqreq::RequestSearchPa
     probe_req.suggest = std::vector<vqreq::RequestSearchPart>{part};
     const FuzzyTable fuzzy = run_suggest_probes(idx, probe_req);
     std::vector<SuggestEntry> out = highlight_part(idx, part, fuzzy.empty() ? nullptr : &fuzzy);
-    std::stable_sort(out.begin(), out.end(), [](const SuggestEntry& a, const SuggestEntry& b) { return a.score > b.score; });  // :189
-    const size_t skip = std::min(part.skip.value_or(0), out.size());  // apply_top_skip, search.rs:230-239
-    out.erase(out.begin(), out.begin() + skip);
-    if (part.top && out.size() > *part.top) out.resize(*part.top);
+    rank_and_cut_highlight(out, part);
     return out;
+}
+
+// ---- the batched highlight: texts ranked and cut to the page on the device, snippets for the page only
+namespace {
+// VQ_NO_HIGHLIGHT_RANK=1: every part of a highlight batch keeps the host route
+bool highlight_rank_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("VQ_NO_HIGHLIGHT_RANK");
+        return !(e && *e && std::string(e) != "0");
+    }();
+    return on;
+}
+
+// The field's record, made on first use: do tokens_to_text_id and text_id_to_token_ids hold the same (token, text) pairs?  Then every text of
+// a matched token's row has a token row that contains the token (it gets a snippet), and every matched token of a text's row lists the text
+// (the text's hit tokens are its row's tokens inside the matched set).  A field that passes has the first table's values in HBM.
+const Index::HighlightField& highlight_field(const Index& idx, const std::string& path) {
+    Index::HighlightField* f;
+    {
+        std::lock_guard<std::mutex> g(idx.highlight_mu);
+        auto& slot = idx.highlight_fields[path];
+        if (!slot) slot = std::make_unique<Index::HighlightField>();
+        f = slot.get();
+    }
+    std::call_once(f->once, [&] {
+        auto a = idx.kv.find(path + TOKENS_TO_TEXT_ID), b = idx.kv.find(path + ".text_id_to_token_ids");
+        if (a == idx.kv.end() || b == idx.kv.end()) return;
+        const KVStore &t2t = a->second, &tokens = b->second;
+        if (idx.sharded() && !t2t.text_csr) return;  // (only that case is known to keep the whole table on every shard)
+        if (t2t.host_values.empty()) return;
+        std::vector<uint64_t> p1, p2;  // token << 32 | text
+        p1.reserve(t2t.host_values.size());
+        p2.reserve(tokens.host_values.size());
+        uint32_t max_text = 0;
+        for (uint32_t r = 0; r < t2t.num_keys; ++r)
+            for (uint64_t k = t2t.host_off[r]; k < t2t.host_off[r + 1]; ++k) {
+                p1.push_back((uint64_t(t2t.key_base) + r) << 32 | t2t.host_values[k]);
+                max_text = std::max(max_text, t2t.host_values[k]);
+            }
+        for (uint32_t r = 0; r < tokens.num_keys; ++r)
+            for (uint64_t k = tokens.host_off[r]; k < tokens.host_off[r + 1]; ++k) p2.push_back(uint64_t(tokens.host_values[k]) << 32 | (uint64_t(tokens.key_base) + r));
+        auto canon = [](std::vector<uint64_t>& v) {
+            std::sort(v.begin(), v.end());
+            v.erase(std::unique(v.begin(), v.end()), v.end());
+        };
+        parallel_for(2, std::min<size_t>(host_threads(), 2), [&](size_t i) { canon(i ? p2 : p1); });
+        if (p1 != p2 || max_text == 0xFFFFFFFFu || (uint64_t(max_text) + 1) * 4 > kTextRankBudget) return;
+        f->num_texts = max_text + 1;
+        f->t2t = &t2t;
+        f->tokens = &tokens;
+        if (t2t.text_csr) f->d_vals = t2t.d_text_vals.as<uint32_t>();
+        else {  // not staged by the index build (an identity field): now, once
+            f->own_vals.alloc(t2t.host_values.size() * 4 + 16);
+            f->own_vals.upload(t2t.host_values.data(), t2t.host_values.size() * 4);
+            f->d_vals = f->own_vals.as<uint32_t>();
+        }
+        f->ok = true;
+    });
+    return *f;
+}
+
+struct TextRankSlot {
+    uint32_t top_n = 0;
+    std::vector<TextRowD> rows;                          // (slot filled in by the round)
+    std::vector<std::pair<uint32_t, uint32_t>> picked;   // result: (text, score bits) sorted by (bits descending, text ascending)
+    uint32_t touched = 0;                                // result: texts that hold a matched token
+};
+// the row of `len` values at `start` with score `bits`, in pieces of at most kTextRankSplit values
+void add_text_rows(TextRankSlot& s, uint64_t start, uint64_t len, uint32_t bits) {
+    for (uint64_t at = 0; at < len; at += kTextRankSplit) s.rows.push_back(TextRowD{start + at, uint32_t(std::min<uint64_t>(kTextRankSplit, len - at)), 0u, bits, 0u});
+}
+// k_text_best + k_text_select over `slots` of one table, in rounds whose `best` arrays fit kTextRankBudget; one download per round
+void run_text_rank(bool timed, Workspace& ws, DevBuf& d_best, DevBuf& d_meta, hipStream_t st, const uint32_t* d_vals, uint32_t num_texts, std::vector<TextRankSlot*>& slots) {
+    const size_t per_round = std::max<size_t>(1, kTextRankBudget / (size_t(num_texts) * 4));
+    for (size_t s0 = 0; s0 < slots.size(); s0 += per_round) {
+        const size_t ns = std::min(per_round, slots.size() - s0);
+        std::vector<TextRowD> rows;
+        std::vector<uint32_t> top_ns(ns);
+        uint32_t stride = 1;
+        uint64_t values = 0;
+        for (size_t k = 0; k < ns; ++k) {
+            TextRankSlot& S = *slots[s0 + k];
+            if (S.top_n == 0 || S.top_n > kTextRankMaxTop) throw VelociError(ERR_DEVICE, "internal: a text-rank slot outside the kernels' range");
+            top_ns[k] = S.top_n;
+            stride = std::max(stride, S.top_n);
+            for (TextRowD r : S.rows) {
+                r.slot = uint32_t(k);
+                values += r.len;
+                rows.push_back(r);
+            }
+        }
+        // tables: [rows][top_ns] up, [counts: 2 per slot][pairs: stride x 2 per slot] down
+        const size_t top_at = align_up(rows.size() * sizeof(TextRowD), 256), down_at = top_at + align_up(ns * 4, 256), down_words = ns * 2 + ns * size_t(stride) * 2;
+        d_meta.ensure(down_at + down_words * 4 + 16);
+        d_best.ensure(ns * size_t(num_texts) * 4 + 16);
+        uint8_t* meta = d_meta.as<uint8_t>();
+        uint32_t* d_counts = reinterpret_cast<uint32_t*>(meta + down_at);
+        if (!rows.empty()) VQ_HIP(hipMemcpyAsync(meta, rows.data(), rows.size() * sizeof(TextRowD), hipMemcpyHostToDevice, st));
+        VQ_HIP(hipMemcpyAsync(meta + top_at, top_ns.data(), ns * 4, hipMemcpyHostToDevice, st));
+        VQ_HIP(hipMemsetAsync(d_best.p, 0, ns * size_t(num_texts) * 4, st));
+        {  // layout bytes: the row values read plus 4 B per atomic
+            LaunchTimer timer(timed, ws, st, K_TEXT_BEST, values * 8, values * 8, ns);
+            launch_text_best(st, reinterpret_cast<const TextRowD*>(meta), uint32_t(rows.size()), d_vals, num_texts, d_best.as<uint32_t>());
+        }
+        {  // num_texts x 4 B per pass over a slot's array: four radix passes, the count of the threshold's equals, the write
+            LaunchTimer timer(timed, ws, st, K_TEXT_SELECT, uint64_t(ns) * num_texts * 4 * 6, uint64_t(ns) * num_texts * 4, ns);
+            launch_text_select(st, d_best.as<uint32_t>(), num_texts, uint32_t(ns), reinterpret_cast<const uint32_t*>(meta + top_at), stride, d_counts, d_counts + 2 * ns);
+        }
+        VQ_HIP(hipGetLastError());
+        std::vector<uint32_t> down(down_words);
+        VQ_HIP(hipMemcpyAsync(down.data(), d_counts, down_words * 4, hipMemcpyDeviceToHost, st));
+        VQ_HIP(hipStreamSynchronize(st));
+        for (size_t k = 0; k < ns; ++k) {
+            TextRankSlot& S = *slots[s0 + k];
+            const uint32_t n = down[2 * k];
+            S.touched = down[2 * k + 1];
+            if (n > S.top_n || n > S.touched) throw VelociError(ERR_DEVICE, "text rank: more pairs than the slot asked for");
+            const uint32_t* pairs = down.data() + 2 * ns + k * size_t(stride) * 2;
+            S.picked.resize(n);
+            for (uint32_t j = 0; j < n; ++j) S.picked[j] = {pairs[2 * j], pairs[2 * j + 1]};
+            std::sort(S.picked.begin(), S.picked.end(), [](auto& a, auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });
+        }
+    }
+}
+}  // namespace
+
+void debug_text_rank(const uint64_t* row_off, const uint32_t* vals, const uint32_t* bits, uint32_t num_rows, uint32_t num_texts, uint32_t top_n,
+                     std::vector<std::pair<uint32_t, uint32_t>>& picked, uint32_t* touched) {
+    Workspace ws;  // (untimed: only handed through)
+    DevBuf d_vals, d_best, d_meta;
+    const uint64_t n_vals = num_rows ? row_off[num_rows] : 0;
+    d_vals.alloc(n_vals * 4 + 16);
+    if (n_vals) d_vals.upload(vals, n_vals * 4);
+    TextRankSlot slot;
+    slot.top_n = top_n;
+    for (uint32_t r = 0; r < num_rows; ++r) add_text_rows(slot, row_off[r], row_off[r + 1] - row_off[r], bits[r]);
+    std::vector<TextRankSlot*> slots{&slot};
+    run_text_rank(false, ws, d_best, d_meta, nullptr, d_vals.as<uint32_t>(), num_texts, slots);
+    picked = std::move(slot.picked);
+    *touched = slot.touched;
+}
+
+void run_highlight_batch(const Index& idx, const vqreq::RequestSearchPart* const* parts_in, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
+                         std::vector<std::string>& errors) {
+    out.assign(n, {});
+    status.assign(n, 0);
+    errors.assign(n, std::string());
+    if (!n) return;
+    VQ_HIP(hipSetDevice(idx.device));
+    // the parts with their terms normalised (search_field.rs:234), and the dictionary scans of all of them in one table
+    std::vector<vqreq::RequestSearchPart> parts(n);
+    vqreq::Request probe_req;
+    probe_req.suggest = std::vector<vqreq::RequestSearchPart>();
+    for (size_t i = 0; i < n; ++i) {
+        if (!parts_in[i]) {
+            status[i] = vqreq::ERR_INVALID_ARGUMENT;
+            errors[i] = "null request";
+            continue;
+        }
+        parts[i] = *parts_in[i];
+        for (auto& t : parts[i].terms) t = vqtext::normalize_text(t);
+        probe_req.suggest->push_back(parts[i]);
+    }
+    FuzzyTable fuzzy;
+    collect_suggest_probes(idx, probe_req, fuzzy);
+    Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
+    std::unique_lock<std::mutex> lock(ws.mu);
+    ws.timed.clear();
+    ws.ev_used = 0;
+    hipStream_t st = idx.pre_stream ? idx.pre_stream : idx.stream;
+    if (!fuzzy.empty()) run_fuzzy_probes(idx, ws, fuzzy, st);
+    auto fail = [&](size_t i, const VelociError& e) {
+        status[i] = e.code;
+        errors[i] = e.what();
+        out[i].clear();
+    };
+    // every part's matched tokens, by the single call's own code
+    std::vector<HighlightLookup> looked(n);
+    std::vector<uint8_t> on_device(n, 0);
+    const size_t threads = std::min(host_threads(), n);
+    parallel_for(n, threads, [&](size_t i) {
+        if (status[i] != 0) return;
+        try {
+            looked[i] = highlight_lookup(idx, parts[i], fuzzy.empty() ? nullptr : &fuzzy);
+        } catch (const VelociError& e) {
+            return fail(i, e);
+        }
+        const vqreq::RequestSearchPart& p = parts[i];
+        const HighlightLookup& lk = looked[i];
+        bool ok = highlight_rank_enabled() && lk.tokenized && lk.add_snippets && p.top && !lk.hits_scores.empty() && *p.top <= kTextRankMaxTop &&
+                  p.skip.value_or(0) <= kTextRankMaxTop && *p.top + p.skip.value_or(0) >= 1 && *p.top + p.skip.value_or(0) <= kTextRankMaxTop;
+        for (auto& h : lk.hits_scores) ok = ok && std::isfinite(h.second) && h.second > 0.0f;
+        on_device[i] = ok;
+    });
+    // the device parts: the field's record (the store check and the staging happen here, on this thread), one slot per distinct part
+    std::map<std::string, std::vector<TextRankSlot*>> by_field;
+    std::map<std::string, std::unique_ptr<TextRankSlot>> slot_of_key;
+    std::vector<TextRankSlot*> slot_of_part(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        if (status[i] != 0 || !on_device[i]) continue;
+        const HighlightLookup& lk = looked[i];
+        const Index::HighlightField& f = highlight_field(idx, lk.path);
+        if (!f.ok) {
+            on_device[i] = 0;
+            continue;
+        }
+        const uint32_t top_n = uint32_t(*parts[i].top + parts[i].skip.value_or(0));
+        std::string key = lk.path;
+        key.push_back('\0');
+        key.append(reinterpret_cast<const char*>(&top_n), 4);
+        key.append(reinterpret_cast<const char*>(lk.hits_scores.data()), lk.hits_scores.size() * sizeof(lk.hits_scores[0]));
+        auto& slot = slot_of_key[key];
+        if (!slot) {
+            slot = std::make_unique<TextRankSlot>();
+            slot->top_n = top_n;
+            for (auto& h : lk.hits_scores) {
+                if (h.first < f.t2t->key_base || h.first - f.t2t->key_base >= f.t2t->num_keys) continue;  // (KVStore::host_row: no row)
+                const uint32_t r = h.first - f.t2t->key_base;
+                uint32_t bits;
+                std::memcpy(&bits, &h.second, 4);
+                add_text_rows(*slot, f.t2t->host_off[r], f.t2t->host_off[r + 1] - f.t2t->host_off[r], bits);
+            }
+            by_field[lk.path].push_back(slot.get());
+        }
+        slot_of_part[i] = slot.get();
+    }
+    for (auto& [path, slots] : by_field) {
+        const Index::HighlightField& f = highlight_field(idx, path);
+        run_text_rank(idx.profile.enabled, ws, ws.d_trank_best, ws.d_trank_meta, st, f.d_vals, f.num_texts, slots);
+    }
+    if (idx.profile.enabled) {  // (every launch above is behind a host synchronisation)
+        std::lock_guard<std::mutex> g(idx.profile_mutex);
+        account_timed_launches(idx.profile, ws);
+    }
+    lock.unlock();
+    // finish: a device part sorts nothing more — its slot is ranked — and builds the page's snippets; every other part takes the host route
+    std::atomic<uint64_t> device_parts{0}, snippets{0};
+    parallel_for(n, threads, [&](size_t i) {
+        if (status[i] != 0) return;
+        const vqreq::RequestSearchPart& p = parts[i];
+        const HighlightLookup& lk = looked[i];
+        try {
+            const TextRankSlot* S = slot_of_part[i];
+            bool done = false;
+            if (S && S->touched != 0) {  // (no touched text: the host route answers that case, or fails as the single call does)
+                std::vector<uint32_t> wanted;
+                for (auto& h : lk.hits_scores) wanted.push_back(h.first);
+                std::sort(wanted.begin(), wanted.end());
+                const size_t skip = std::min<size_t>(p.skip.value_or(0), S->picked.size());
+                const size_t end = std::min<size_t>(S->picked.size(), skip + *p.top);
+                done = true;
+                for (size_t k = skip; k < end && done; ++k) {
+                    SuggestEntry e;
+                    e.term_id = S->picked[k].first;
+                    std::memcpy(&e.score, &S->picked[k].second, 4);
+                    done = highlight_snippet(idx, lk, p, e.term_id, wanted, &e.text);  // (the store check rules a miss out)
+                    out[i].push_back(std::move(e));
+                }
+                if (done) {
+                    device_parts.fetch_add(1, std::memory_order_relaxed);
+                    snippets.fetch_add(out[i].size(), std::memory_order_relaxed);
+                } else out[i].clear();
+            }
+            if (!done) {
+                out[i] = highlight_resolve(idx, p, lk);
+                snippets.fetch_add(out[i].size(), std::memory_order_relaxed);  // (one per text that holds a matched token)
+                rank_and_cut_highlight(out[i], p);
+            }
+        } catch (const VelociError& e) {
+            fail(i, e);
+        }
+    });
+    idx.highlight_device_parts.fetch_add(device_parts.load(), std::memory_order_relaxed);
+    idx.highlight_snippets_built.fetch_add(snippets.load(), std::memory_order_relaxed);
 }
 
 // The continuation of a request behind the ranked hit (score, id): the next kMaxTopK hits below that key, no facets (page 0 counted them)

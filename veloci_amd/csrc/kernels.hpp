@@ -149,6 +149,24 @@ void launch_dict_topn(hipStream_t st, const TopnProbeD* probes, uint32_t n_probe
 int debug_dict_topn(const uint32_t* terms, const uint32_t* classes, uint32_t n, uint32_t top_n, const uint16_t* class_ord_host, uint32_t* out_terms, uint32_t* out_classes,
                     uint32_t* out_n);
 
+// ---- text ranking of the batched highlight (text_rank.hip): best matched-token score per text, then the page's texts selected per slot
+struct TextRowD {  // one piece of a matched token's tokens_to_text_id row
+    uint64_t start;  // first value of the piece inside the staged values
+    uint32_t len;    // values of the piece (at most kTextRankSplit)
+    uint32_t slot;   // the part's `best` array
+    uint32_t bits;   // the token's f32 score bits: finite and > 0
+    uint32_t pad;
+};
+constexpr uint32_t kTextRankSplit = 4096;              // values one wave streams: a longer row goes in several descriptors
+constexpr uint32_t kTextRankMaxTop = 1024;             // top + skip a slot may ask for
+constexpr size_t kTextRankBudget = size_t(128) << 20;  // bytes of `best` arrays (num_texts x 4 B per slot) one round may use
+// best[slot * num_texts + text] = max(best, bits) for every value `text` < num_texts of every row piece (`best` zero-filled before)
+void launch_text_best(hipStream_t st, const TextRowD* rows, uint32_t n_rows, const uint32_t* vals, uint32_t num_texts, uint32_t* best);
+// per slot: the top_ns[slot] (<= out_stride) best non-zero entries by (bits descending, text ascending) as (text, bits) pairs at
+// out_pairs[slot * out_stride * 2 ...) in no order; out_counts[2 * slot] = pairs written, out_counts[2 * slot + 1] = non-zero entries
+void launch_text_select(hipStream_t st, const uint32_t* best, uint32_t num_texts, uint32_t n_slots, const uint32_t* top_ns, uint32_t out_stride, uint32_t* out_counts,
+                        uint32_t* out_pairs);
+
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst
     uint64_t src, dst;

@@ -219,6 +219,17 @@ def highlight_text(text, terms, snippet_info=None, tokenized=True):
 def suggest_batch(requests, index, raise_on_error=True):
     """n independent suggest requests (each as `suggest` takes it) answered as one device batch (`vq_suggest_batch`).
     -> one [(text, score, term_id)] per request; a failing request raises, or with raise_on_error=False yields its VelociError."""
+    return _entry_batch(_lib.lib().vq_suggest_batch, requests, index, raise_on_error)
+
+
+def highlight_batch(parts, index, raise_on_error=True):
+    """n independent highlight parts (each as `highlight` takes it) answered as one device batch (`vq_highlight_batch`): the dictionary scans run
+    together, a part with `snippet` and its own `top` has its texts ranked and cut to the page on the device and only the page's snippets built.
+    -> one [(snippet, score, text_id)] per part; a failing part raises, or with raise_on_error=False yields its VelociError."""
+    return _entry_batch(_lib.lib().vq_highlight_batch, parts, index, raise_on_error)
+
+
+def _entry_batch(entry, requests, index, raise_on_error):
     L = _lib.lib()
     texts = []
     for r in requests:
@@ -230,7 +241,7 @@ def suggest_batch(requests, index, raise_on_error=True):
     lens = (C.c_size_t * n)(*[len(t) for t in texts])
     outs = (C.c_void_p * n)()
     status = (C.c_int * n)()
-    _lib.check(L.vq_suggest_batch(index.h, arr, lens, n, outs, status))
+    _lib.check(entry(index.h, arr, lens, n, outs, status))
     first_error = L.vq_last_error().decode("utf-8", "replace")
     results = []
     try:

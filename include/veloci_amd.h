@@ -408,6 +408,42 @@ int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const 
  * writes the best min(top, non-zero counts) entries, returns their number, -1 on failure. */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts);
 
+/* ---- the pre-pass drivers alone (exec.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs): what a batch runs before its
+ * scans, on jobs the caller describes the way the request compiler does, with every list the drivers build copied back whole.  Jobs are passed as a
+ * CSR: job j owns ids[job_off[j] .. job_off[j + 1]) (job_off[0] == 0, at most 2^31 ids, n_jobs >= 1) and names its stores by the paths they were
+ * loaded under.  Lists come back to back in out_docs / out_val_bits (f32 bit patterns), `out_cap` entries each: job j's out_len[j] entries and the
+ * 8 sentinel entries (0xFFFFFFFF, 0.0f) behind them start at the sum of out_len[i] + 8 over i < j.  Every function returns 0; -1 without a device or
+ * when the driver fails; -2 for arguments outside the ranges given here (a null pointer, an unknown path, a store without the device image the
+ * driver reads, an id table that is no CSR, `out_cap` too small for the lists).  With profiling on (vq_profile_enable) the launches are
+ * accounted in vq_profile_json like a batch's. */
+/* K2, the union of posting lists with the per-doc maximum of term_score * (f16 score / 100): job j merges the lists `tokens` (ids below the
+ * store's token count, at least one) of store_paths[j] ("<field>.textindex.to_anchor_id_score") with the term scores term_score_bits (f32 bits,
+ * one per token).  route 0: the shipped rule (more than VQ_UNION_DENSE_MIN lists, 4096 by default, take the dense route of union_dense.hip);
+ * 1: k_union for every job (one level up to 64 lists, two levels up to 4096; more is -2); 2: the dense route for every job.  out_max_bits[j]: the
+ * largest value of job j's list, 0.0f for an empty one. */
+int vq_debug_union_lists(const vq_index*, const char* const* store_paths, const uint64_t* job_off, const uint32_t* tokens, const uint32_t* term_score_bits,
+                         uint32_t n_jobs, int route, uint64_t out_cap, uint32_t* out_len, uint32_t* out_max_bits, uint32_t* out_docs, uint32_t* out_val_bits);
+/* K7, text locality of a field whose text ids are not anchors: job j gathers the rows of `tokens` (multiplicity kept; ids outside the table are
+ * skipped) from t2t_paths[j] ("<field>.textindex.tokens_to_text_id" of a column that is not an anchor identity column) and expands the texts that
+ * occur c > 1 times through t2a_paths[j] ("<field>.textindex.text_id_to_anchor") to (anchor, 2 * c * c), the smallest value per anchor, ascending
+ * anchors of this shard.  When no job of the call gathers any entry nothing is launched: every out_len is 0 and the out arrays are left alone. */
+int vq_debug_locality_lists(const vq_index*, const char* const* t2t_paths, const char* const* t2a_paths, const uint64_t* job_off, const uint32_t* tokens,
+                            uint32_t n_jobs, uint64_t out_cap, uint32_t* out_len, uint32_t* out_docs, uint32_t* out_val_bits);
+/* k_range_hits: job j counts the postings of the lists `tokens` (token_off CSR; ids below the token count; none, one — a lane per anchor — or
+ * several — a workgroup per anchor) of store_paths[j] around its anchors (anchor_off CSR; strictly ascending, below 0xFFFFFFFF).  out_counts takes
+ * 2 * anchor_off[n_jobs] numbers: [2k] the postings at anchor k, [2k + 1] those strictly between the job's previous anchor and anchor k (0 for a job's
+ * first).  A sharded index needs vq_index_set_allreduce (the driver sums over the shards), else -2. */
+int vq_debug_range_hits(const vq_index*, const char* const* store_paths, const uint64_t* token_off, const uint32_t* tokens, const uint64_t* anchor_off,
+                        const uint32_t* anchors, uint32_t n_jobs, uint64_t* out_counts);
+/* K10, a 1:n boost list: job j gathers the value ids of `text_ids` (ids outside the table are skipped) from to_parent_paths[j]
+ * ("<leaf>.textindex.value_id_to_parent"), sorts them and maps every one that has a boost value in boost_paths[j] ("<boost>.boost_valid_to_value")
+ * and a non-empty row in to_anchor_paths[j] ("<boost>.value_id_to_anchor") to (first anchor of the row, boost value), in value-id order.  The list
+ * holds the pairs of this shard's anchors (out_len[j]); out_total[j] counts the pairs of all shards; out_flags[j]: bit 0 = the anchors never
+ * decrease in value-id order, bit 1 = some anchor equals its predecessor. */
+int vq_debug_boost1n_lists(const vq_index*, const char* const* to_parent_paths, const char* const* to_anchor_paths, const char* const* boost_paths,
+                           const uint64_t* job_off, const uint32_t* text_ids, uint32_t n_jobs, uint64_t out_cap, uint32_t* out_len, uint32_t* out_total,
+                           uint32_t* out_flags, uint32_t* out_docs, uint32_t* out_val_bits);
+
 const char* vq_version(void);
 
 #ifdef __cplusplus

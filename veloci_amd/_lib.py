@@ -22,7 +22,8 @@ SYMBOLS = [
     "vq_partial_hist_device_ptr", "vq_merge_partials", "vq_merge_partials_flat", "vq_partial_free",
     "vq_search_batch_partial_at", "vq_partial_slots", "vq_index_partial_arena_ptr", "vq_partial_total_bytes", "vq_merge_partials_flat_strided",
     "vq_comm_unique_id", "vq_comm_init", "vq_comm_init_custom", "vq_comm_destroy", "vq_shard_step_begin", "vq_shard_step_end", "vq_shard_step_free", "vq_shard_step_flat",
-    "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_version",
+    "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_debug_union_lists", "vq_debug_locality_lists",
+    "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_version",
 ]
 COMM_ID_BYTES = 128
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -129,6 +130,10 @@ def lib():
         "vq_debug_dict_topn": (i, [vp, vp, u32, u32, vp, vp, C.POINTER(u32)]),
         "vq_index_highlight_rank_counts": (None, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "vq_debug_text_rank": (i, [vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(u32)]),
+        "vq_debug_union_lists": (i, [vp, C.POINTER(cp), vp, vp, vp, u32, i, u64, vp, vp, vp, vp]),
+        "vq_debug_locality_lists": (i, [vp, C.POINTER(cp), C.POINTER(cp), vp, vp, u32, u64, vp, vp, vp]),
+        "vq_debug_range_hits": (i, [vp, C.POINTER(cp), vp, vp, vp, vp, u32, vp]),
+        "vq_debug_boost1n_lists": (i, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(cp), vp, vp, u32, u64, vp, vp, vp, vp, vp]),
         "vq_merge_partials": (i, [vp, vp, vp, u32, C.POINTER(vp), C.POINTER(i)]),
         "vq_merge_partials_flat": (i, [vp, vp, vp, u32, sz, vp, vp, vp, vp, vp]),
         "vq_partial_free": (None, [vp]),

@@ -234,6 +234,50 @@ void dump_parts(std::string& s, const std::optional<std::vector<vqreq::RequestSe
 }
 }  // namespace
 
+// ---- helpers of the vq_debug_*_lists functions below
+namespace {
+std::string debug_job_key(uint32_t j) {  // the job tables are ordered by key: keys in job order
+    char buf[16];
+    std::snprintf(buf, sizeof buf, "%010u", j);
+    return buf;
+}
+bool debug_csr_ok(const uint64_t* off, const uint32_t* ids, uint32_t n_jobs) {
+    if (!off || off[0] != 0) return false;
+    for (uint32_t j = 0; j < n_jobs; ++j)
+        if (off[j + 1] < off[j]) return false;
+    return off[n_jobs] <= (uint64_t(1) << 31) && (ids || !off[n_jobs]);
+}
+// the lists of the jobs, back to back: job j's len[j] + 8 entries start at the sum of len[i] + 8 over i < j.  False when out_cap is too small.
+// A job without a list on the device (the driver launched nothing for the whole call) leaves its 8 entries as they are.
+template <class Job>
+bool debug_copy_lists(const std::vector<const Job*>& jobs, uint64_t out_cap, uint32_t* out_docs, uint32_t* out_val_bits) {
+    uint64_t need = 0;
+    for (const Job* j : jobs) need += uint64_t(j->len) + 8;
+    if (need > out_cap) return false;
+    uint64_t at = 0;
+    for (const Job* j : jobs) {
+        if (j->d_docs && j->d_vals) {
+            VQ_HIP(hipMemcpy(out_docs + at, j->d_docs, (size_t(j->len) + 8) * 4, hipMemcpyDeviceToHost));
+            VQ_HIP(hipMemcpy(out_val_bits + at, j->d_vals, (size_t(j->len) + 8) * 4, hipMemcpyDeviceToHost));
+        }
+        at += uint64_t(j->len) + 8;
+    }
+    return true;
+}
+template <class F>
+int debug_run(const vq_index* index, F body) {  // body returns false for an output area that is too small
+    try {
+        bool fits = true;
+        vq::debug_prepass(*index->idx, [&](Workspace& ws, hipStream_t st) { fits = body(ws, st); });
+        g_err.clear();
+        return fits ? 0 : -2;
+    } catch (const std::exception& e) {
+        g_err = e.what();  // (vq_last_error says why)
+        return -1;
+    }
+}
+}  // namespace
+
 extern "C" {
 
 const char* vq_last_error(void) { return g_err.c_str(); }
@@ -300,6 +344,133 @@ int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const 
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts) {
     if (!hist || !out_values || !out_counts) return -1;
     return vq::debug_facet_select(hist, num_values, top, misalign, out_values, out_counts);
+}
+
+/* self-checks (tests): the pre-pass drivers of exec.cpp alone — the jobs described as the compiler describes them, run by run_*_jobs, every
+   job's whole (doc, f32) list copied back with its 8 sentinel entries.  0; -1 without a device (or when the driver fails); -2 for arguments
+   outside the documented ranges */
+
+int vq_debug_union_lists(const vq_index* index, const char* const* store_paths, const uint64_t* job_off, const uint32_t* tokens, const uint32_t* term_score_bits,
+                         uint32_t n_jobs, int route, uint64_t out_cap, uint32_t* out_len, uint32_t* out_max_bits, uint32_t* out_docs, uint32_t* out_val_bits) {
+    if (!index || !n_jobs || !store_paths || !debug_csr_ok(job_off, tokens, n_jobs) || !term_score_bits || route < 0 || route > 2 || !out_len || !out_max_bits ||
+        !out_docs || !out_val_bits)
+        return -2;
+    UnionTable table;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        auto it = store_paths[j] ? index->idx->postings.find(store_paths[j]) : index->idx->postings.end();
+        if (it == index->idx->postings.end()) return -2;
+        const uint64_t n = job_off[j + 1] - job_off[j];
+        if (n == 0 || (route == 1 && n > 64 * 64)) return -2;  // (the compiler asks for no union without lists; two levels of k_union take 64 x 64)
+        UnionJob job;
+        job.key = debug_job_key(j);
+        for (uint64_t k = job_off[j]; k < job_off[j + 1]; ++k) {
+            if (tokens[k] >= it->second.num_tokens) return -2;
+            UnionJob::Term t{&it->second, tokens[k], 0.0f};
+            std::memcpy(&t.score, &term_score_bits[k], 4);
+            job.terms.push_back(t);
+        }
+        table.emplace(job.key, std::move(job));
+    }
+    return debug_run(index, [&](Workspace& ws, hipStream_t st) {
+        vq::run_union_jobs(*index->idx, ws, table, st, route == 0 ? -1 : route == 1 ? 64 * 64 : 0);
+        std::vector<const UnionJob*> jobs;
+        for (auto& kv : table) jobs.push_back(&kv.second);
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            out_len[j] = jobs[j]->len;
+            std::memcpy(&out_max_bits[j], &jobs[j]->max_value, 4);
+        }
+        return debug_copy_lists(jobs, out_cap, out_docs, out_val_bits);
+    });
+}
+
+int vq_debug_locality_lists(const vq_index* index, const char* const* t2t_paths, const char* const* t2a_paths, const uint64_t* job_off, const uint32_t* tokens,
+                            uint32_t n_jobs, uint64_t out_cap, uint32_t* out_len, uint32_t* out_docs, uint32_t* out_val_bits) {
+    if (!index || !n_jobs || !t2t_paths || !t2a_paths || !debug_csr_ok(job_off, tokens, n_jobs) || !out_len || !out_docs || !out_val_bits) return -2;
+    LocalityTable table;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        auto t2t = t2t_paths[j] ? index->idx->kv.find(t2t_paths[j]) : index->idx->kv.end();
+        auto t2a = t2a_paths[j] ? index->idx->kv.find(t2a_paths[j]) : index->idx->kv.end();
+        // the images the driver reads: the token -> text table as a CSR, the text -> anchor rows with their row table
+        if (t2t == index->idx->kv.end() || t2a == index->idx->kv.end() || !t2t->second.text_csr || !t2a->second.list_rows || !t2a->second.d_row_start.p) return -2;
+        LocalityJob job;
+        job.key = debug_job_key(j);
+        job.t2t_path = t2t_paths[j];
+        job.t2a_path = t2a_paths[j];
+        job.tokens.assign(tokens + job_off[j], tokens + job_off[j + 1]);
+        table.emplace(job.key, std::move(job));
+    }
+    return debug_run(index, [&](Workspace& ws, hipStream_t st) {
+        vq::run_locality_jobs(*index->idx, ws, table, st);
+        std::vector<const LocalityJob*> jobs;
+        for (auto& kv : table) jobs.push_back(&kv.second);
+        for (uint32_t j = 0; j < n_jobs; ++j) out_len[j] = jobs[j]->len;
+        return debug_copy_lists(jobs, out_cap, out_docs, out_val_bits);
+    });
+}
+
+int vq_debug_range_hits(const vq_index* index, const char* const* store_paths, const uint64_t* token_off, const uint32_t* tokens, const uint64_t* anchor_off,
+                        const uint32_t* anchors, uint32_t n_jobs, uint64_t* out_counts) {
+    if (!index || !n_jobs || !store_paths || !debug_csr_ok(token_off, tokens, n_jobs) || !debug_csr_ok(anchor_off, anchors, n_jobs) || !out_counts) return -2;
+    if (index->idx->sharded() && !index->idx->allreduce_fn) return -2;  // (the driver sums the counts over the shards)
+    RangeTable table;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        auto it = store_paths[j] ? index->idx->postings.find(store_paths[j]) : index->idx->postings.end();
+        if (it == index->idx->postings.end()) return -2;
+        RangeJob job;
+        job.key = debug_job_key(j);
+        job.store_path = store_paths[j];
+        job.tokens.assign(tokens + token_off[j], tokens + token_off[j + 1]);
+        for (uint32_t t : job.tokens)
+            if (t >= it->second.num_tokens) return -2;
+        auto an = std::make_shared<std::vector<uint32_t>>(anchors + anchor_off[j], anchors + anchor_off[j + 1]);
+        for (size_t k = 0; k < an->size(); ++k)
+            if ((*an)[k] == 0xFFFFFFFFu || (k && (*an)[k - 1] >= (*an)[k])) return -2;
+        job.anchors = std::move(an);
+        table.emplace(job.key, std::move(job));
+    }
+    return debug_run(index, [&](Workspace& ws, hipStream_t st) {
+        vq::run_range_jobs(*index->idx, ws, table, UnionTable(), st);
+        uint64_t at = 0;
+        for (auto& kv : table) {
+            std::copy(kv.second.counts.begin(), kv.second.counts.end(), out_counts + at);
+            at += kv.second.counts.size();
+        }
+        return true;
+    });
+}
+
+int vq_debug_boost1n_lists(const vq_index* index, const char* const* to_parent_paths, const char* const* to_anchor_paths, const char* const* boost_paths,
+                           const uint64_t* job_off, const uint32_t* text_ids, uint32_t n_jobs, uint64_t out_cap, uint32_t* out_len, uint32_t* out_total,
+                           uint32_t* out_flags, uint32_t* out_docs, uint32_t* out_val_bits) {
+    if (!index || !n_jobs || !to_parent_paths || !to_anchor_paths || !boost_paths || !debug_csr_ok(job_off, text_ids, n_jobs) || !out_len || !out_total || !out_flags ||
+        !out_docs || !out_val_bits)
+        return -2;
+    Boost1nTable table;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        auto tp = to_parent_paths[j] ? index->idx->kv.find(to_parent_paths[j]) : index->idx->kv.end();
+        auto ta = to_anchor_paths[j] ? index->idx->kv.find(to_anchor_paths[j]) : index->idx->kv.end();
+        auto bc = boost_paths[j] ? index->idx->boost.find(boost_paths[j]) : index->idx->boost.end();
+        // the images the driver reads: both tables as whole CSRs in HBM
+        if (tp == index->idx->kv.end() || ta == index->idx->kv.end() || bc == index->idx->boost.end() || !tp->second.value_csr || !ta->second.value_csr) return -2;
+        Boost1nJob job;
+        job.key = debug_job_key(j);
+        job.to_parent_path = to_parent_paths[j];
+        job.to_anchor_path = to_anchor_paths[j];
+        job.boost_path = boost_paths[j];
+        job.text_ids.assign(text_ids + job_off[j], text_ids + job_off[j + 1]);
+        table.emplace(job.key, std::move(job));
+    }
+    return debug_run(index, [&](Workspace& ws, hipStream_t st) {
+        vq::run_boost1n_jobs(*index->idx, ws, table, st);
+        std::vector<const Boost1nJob*> jobs;
+        for (auto& kv : table) jobs.push_back(&kv.second);
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            out_len[j] = jobs[j]->len;
+            out_total[j] = jobs[j]->total;
+            out_flags[j] = (jobs[j]->ascending ? 1u : 0u) | (jobs[j]->several ? 2u : 0u);
+        }
+        return debug_copy_lists(jobs, out_cap, out_docs, out_val_bits);
+    });
 }
 
 // ------------------------------------------------------------------ index

@@ -742,7 +742,10 @@ CompiledQuery compile_query(const Index& idx, const vqreq::Request& req, const C
 void run_locality_jobs(const Index& idx, Workspace& ws, LocalityTable& table, hipStream_t st);
 void run_boost1n_jobs(const Index& idx, Workspace& ws, Boost1nTable& table, hipStream_t st);
 void run_range_jobs(const Index& idx, Workspace& ws, RangeTable& table, const UnionTable& unions, hipStream_t st);
-void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st);
+// dense_min: a job with more lists takes the dense route (at most 64 x 64, what two levels of k_union take); negative: the shipped rule
+// (VQ_UNION_DENSE_MIN, else 64 x 64)
+void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st, int64_t dense_min = -1);
+void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStream_t)>& body);  // exec.cpp: what vq_debug_*_lists run the drivers in
 struct Result;
 // Deep requests (top + skip > kMaxTopK) of an unsharded batch: results[i] holds page 0; fetch the following pages (each one scan that
 // ranks only keys below the previous page's last) and cut the requested window.

@@ -870,12 +870,13 @@ void run_union_dense(const Index& idx, Workspace& ws, const std::vector<UnionJob
 }
 }  // namespace
 
-void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st) {
+void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st, int64_t dense_min) {
+    const size_t dense_above = dense_min < 0 ? union_dense_min() : std::min<size_t>(size_t(dense_min), 64 * 64);  // (two levels of k_union take no more than 64 x 64)
     std::vector<UnionTaskH> l1, l2;
     std::vector<UnionJob*> dense;
     for (auto& kv : table) {
         UnionJob& job = kv.second;
-        if (job.terms.size() > union_dense_min()) {  // (the lists that are non-empty in the unsharded index: every shard takes the same route)
+        if (job.terms.size() > dense_above) {  // (the lists that are non-empty in the unsharded index: every shard takes the same route)
             dense.push_back(&job);
             continue;
         }
@@ -1858,6 +1859,23 @@ static void account_timed_launches(Profile& P, Workspace& ws) {
         k.queries += t.queries;
     }
     ws.timed.clear();
+}
+
+// vq_debug_*_lists (capi.cpp): pre-pass drivers alone, on the next workspace in turn (held until `body` returns: the drivers' results live in
+// it, `body` reads them back) and on the pre-passes' stream; their timed launches go to the profile like a batch's
+void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStream_t)>& body) {
+    VQ_HIP(hipSetDevice(idx.device));
+    Workspace& ws = idx.ws[idx.next_ws.fetch_add(1) % kWorkspaces];
+    std::unique_lock<std::mutex> lock(ws.mu);
+    ws.timed.clear();
+    ws.ev_used = 0;
+    const hipStream_t st = idx.pre_stream ? idx.pre_stream : idx.stream;
+    body(ws, st);
+    VQ_HIP(hipStreamSynchronize(st));
+    if (idx.profile.enabled) {
+        std::lock_guard<std::mutex> g(idx.profile_mutex);
+        account_timed_launches(idx.profile, ws);
+    }
 }
 
 // The dictionary scans of a suggest / highlight request, answered: on the next workspace in turn, on the pre-passes' stream

@@ -173,6 +173,29 @@ int vq_debug_compile(const vq_index*, const vq_request*);
  * `states` / `classes` may be null. */
 int vq_debug_regex_compile(const vq_index*, const char* part_json, size_t len, uint32_t* states, uint32_t* classes);
 
+/* --------------------------------------------------------------- doc sets
+ *
+ * A set of anchor ids staged in HBM and attached to requests: the request then behaves exactly as if its `filter` were one leaf whose hits_ids are
+ * the set's ids (a leaf with a label of its own), and-ed with the request's own `filter` when it has one.  Nothing else about the request
+ * changes: vq_request_to_json prints the same text, no JSON key exists for it.  A doc set is immutable; any number of requests and threads may
+ * share one.  It belongs to the index it was made for: a search that pairs it with another index answers VQ_ERR_INVALID_ARGUMENT for that request. */
+typedef struct vq_docset vq_docset;
+/* ids: n u32 anchor ids, any order, duplicates allowed; ids_on_device != 0: `ids` is device memory on the index's GPU (4-byte aligned, complete before
+ * the call).  VQ_ERR_INVALID_ARGUMENT when an id is >= the index's number of anchors (the count is in vq_last_error).  Synchronous. */
+int vq_docset_create(const vq_index*, const uint32_t* ids, uint64_t n, int ids_on_device, vq_docset** out);
+uint64_t vq_docset_len(const vq_docset*);        /* unique ids of the whole set (the same on every shard) */
+uint64_t vq_docset_local_len(const vq_docset*);  /* those inside this index's doc range */
+uint64_t vq_docset_device_bytes(const vq_docset*);
+/* self-check (tests): part 0 = the local ids without padding, 1 = bitmap words, 2 = rank_dir, 3 = tile_dir, 4 = the local ids with their padding to
+ * a multiple of 4 entries; returns the element count (0: the set carries no such part), copies min(count, cap) elements */
+uint64_t vq_debug_docset_part(const vq_docset*, int part, uint32_t* out, uint64_t cap);
+/* measurement: with VQ_DOCSET_TIMING=1 in the environment a set records the HIP event times (ms) of its construction — marking the ids, counting and
+ * scanning, expanding; 0, or -1 when the set recorded none */
+int vq_debug_docset_timings(const vq_docset*, float* ms_mark, float* ms_count_scan, float* ms_expand);
+void vq_docset_free(vq_docset*);
+/* attaches the set to the request (NULL detaches).  The request keeps the set alive: freeing the handle afterwards is allowed. */
+int vq_request_set_docset(vq_request*, const vq_docset*);
+
 /* ---------------------------------------------------------------- results
  *
  * `vq_result` == `search::SearchResult` (src/search/result/search_result.rs:9-26). */

@@ -58,6 +58,9 @@ struct vq_index {
 struct vq_request {
     Request req;
 };
+struct vq_docset {
+    std::shared_ptr<const DocSet> set;
+};
 struct vq_result {
     Result r;
 };
@@ -736,6 +739,52 @@ int vq_debug_regex_compile(const vq_index* index, const char* part_json, size_t 
     });
 }
 void vq_request_free(vq_request* r) { delete r; }
+
+// ------------------------------------------------------------------ doc sets
+int vq_docset_create(const vq_index* index, const uint32_t* ids, uint64_t n, int ids_on_device, vq_docset** out) {
+    return guard([&] {
+        if (!index || !out || (n && !ids)) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_create: null argument");
+        *out = nullptr;
+        auto set = vq::make_docset(*index->idx, ids, n, ids_on_device != 0);
+        auto* h = new vq_docset();
+        h->set = std::move(set);
+        *out = h;
+    });
+}
+uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
+uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }
+uint64_t vq_docset_device_bytes(const vq_docset* d) { return d ? d->set->device_bytes : 0; }
+uint64_t vq_debug_docset_part(const vq_docset* d, int part, uint32_t* out, uint64_t cap) {
+    if (!d) return 0;
+    const DocSet& s = *d->set;
+    const DevBuf* src = nullptr;
+    uint64_t count = 0;
+    switch (part) {
+        case 0: src = &s.docs; count = s.local_len; break;
+        case 1: src = &s.bitmap; count = s.bitmap_words; break;
+        case 2: src = &s.rank_dir; count = s.rank_entries; break;
+        case 3: src = &s.tile_dir; count = s.tile_entries; break;
+        case 4: src = &s.docs; count = (uint64_t(s.local_len) + 3u) & ~uint64_t(3); break;
+        default: return 0;
+    }
+    const uint64_t take = std::min(count, cap);
+    if (take && out && src->p && hipMemcpy(out, src->p, take * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    return count;
+}
+int vq_debug_docset_timings(const vq_docset* d, float* ms_mark, float* ms_count_scan, float* ms_expand) {
+    if (!d || d->set->ms_mark < 0.0f) return -1;
+    if (ms_mark) *ms_mark = d->set->ms_mark;
+    if (ms_count_scan) *ms_count_scan = d->set->ms_count_scan;
+    if (ms_expand) *ms_expand = d->set->ms_expand;
+    return 0;
+}
+void vq_docset_free(vq_docset* d) { delete d; }
+int vq_request_set_docset(vq_request* r, const vq_docset* d) {
+    return guard([&] {
+        if (!r) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_request_set_docset: null request");
+        r->req.docset = d ? d->set : nullptr;  // (a copy of the shared_ptr: the request keeps the set alive)
+    });
+}
 // The continuation of `request` behind the ranked hit (score, id): what a caller of the sharded partial / merge path sends for the next page of a
 // request whose top + skip reaches beyond one scan's ranking (vq_result_is_page).
 int vq_request_page_after(const vq_request* request, float score, uint32_t id, vq_request** out) {

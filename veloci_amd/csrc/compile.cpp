@@ -739,7 +739,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                 cq.algorithmic_bytes += 6ull * done->input_postings + 8ull * done->len;
                 info.glen = done->global_len;
                 // the merged length is this shard's only: known globally when the index is not sharded
-                info.len_known = !req.filter && idx.can_sum_over_shards();
+                info.len_known = !req.filtered() && idx.can_sum_over_shards();
             }
             op.list_count = uint16_t(count);
             push_op(ops, op, sp);
@@ -779,7 +779,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         }
         op.list_count = uint16_t(count);
         // a single posting list and no Set filter in front of it: the result length is the list length
-        info.len_known = with_entries <= 1 && !req.filter;
+        info.len_known = with_entries <= 1 && !req.filtered();
         info.glen = 0;
         for (auto& e : entries) info.glen += e.ps->global_len[e.tid];
         push_op(ops, op, sp);
@@ -950,7 +950,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             // (the rest is skipped at the next hit); reached by scanning forward, it gets ALL its entries.  With the entry anchors
             // a_0 < a_1 < ...: a_j is met resting on its first entry iff it is the very first entry, or the leaf has a hit strictly
             // between a_(j-1) and a_j, or a_(j-1) is a hit that was NOT met that way (its scan stopped on a_j's first entry).
-            if (req.filter) unsupported("1:n field boost with several boosted values on one anchor, under a filter (" + b.path + ")");
+            if (req.filtered()) unsupported("1:n field boost with several boosted values on one anchor, under a filter (" + b.path + ")");
             const std::vector<uint32_t>& anchors = entry->anchors;
             const auto& pairs = entry->pairs;
             const RangeJob* done = nullptr;
@@ -1011,6 +1011,40 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         }
     }
 
+
+    // The request's doc set: one more filter leaf over the set's id list, and-ed with the filter tree when there is one — what the request would
+    // compile to if its filter were a leaf whose hits_ids are the set's ids (an empty set: the leaf without lists of an empty text_id_to_anchor row).
+    int docset_list = -1;  // the set's list in cq.lists
+    void emit_docset_leaf(uint32_t& sp) {
+        const DocSet& ds = *req.docset;
+        if (ds.index_uid != idx.uid) throw VelociError(ERR_INVALID_ARGUMENT, "the request's doc set was made for another index");
+        cq.docset = req.docset;
+        DOp op{};
+        op.kind = OP_LEAF;
+        op.list_begin = uint16_t(cq.lists.size());
+        if (ds.len) {
+            HList h;
+            h.d_docs = ds.docs.as<uint32_t>();
+            h.len = ds.local_len;
+            h.global_len = ds.len;
+            if (ds.bitmap.p) {
+                h.flags |= LIST_BITMAP;
+                h.d_bitmap = ds.bitmap.as<uint32_t>();
+                h.d_rank_dir = ds.rank_dir.as<uint32_t>();
+            }
+            if (ds.tile_dir.p) h.d_tile_dir = ds.tile_dir.as<uint32_t>();
+            docset_list = int(add_list(h));
+            cq.algorithmic_bytes += 4ull * h.len;
+            op.list_count = 1;
+        }
+        push_op(cq.fops, op, sp);
+        if (cq.fops.size() > 1) {  // filter AND set (presence only: the pairwise fold of the filter tree)
+            DOp both{};
+            both.kind = OP_AND;
+            both.nchild = 2;
+            push_op(cq.fops, both, sp);
+        }
+    }
 
     NodeInfo compile_node(const SearchRequest& r, bool is_filter, std::vector<DOp>& ops, uint32_t& sp, const std::vector<RequestBoostPart>& boost) {
         NodeInfo info = compile_node_inner(r, is_filter, ops, sp, boost, is_filter ? UINT32_MAX : next_node++);
@@ -1959,6 +1993,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             compile_node(*req.filter, true, cq.fops, sp, {});
             if (cq.fops.empty()) unsupported("filter that reduces to nothing");
         }
+        if (req.docset) emit_docset_leaf(sp);
         sp = 0;
         NodeInfo root = compile_node(*req.search_req, false, cq.ops, sp, req.boost.value_or(std::vector<RequestBoostPart>{}));
         for (uint32_t li : root.cover) cq.lists[li].flags |= LIST_COVER;
@@ -2351,6 +2386,11 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         if (!cq.simple_flags) detect_rich_simple();
         if (!cq.simple_flags) detect_wide();
         cq.kclass = route_query(cq);  // simple_flags is final: everything below — and the launch (exec.cpp) — goes by the class
+        if (docset_list >= 0 && cq.kclass != K_TILE_SCAN) {  // k_tile_scan alone reads an id-only list's bitmap image: the others get the plain id list
+            HList& l = cq.lists[size_t(docset_list)];
+            l.flags &= ~uint32_t(LIST_BITMAP);
+            l.d_bitmap = l.d_rank_dir = nullptr;
+        }
         if (cq.kclass == K_TILE_SCAN || cq.kclass == K_SCAN_WIDE) compute_prune_table();
         if (cq.kclass == K_TILE_SCAN && count_reqs.empty()) {  // k_tile_scan: a dense cover list means every tile gets visited anyway: walk them in order
             bool dense_cover = false;                   // and read the dense lists as bitmap images instead of scattering them

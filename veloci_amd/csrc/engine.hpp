@@ -576,6 +576,7 @@ struct Index {
     mutable std::atomic<uint64_t> or_reruns{0};  // requests that ran a second time because k_scan_probe_or's short cut could not be confirmed (tests, tools)
     mutable std::unique_ptr<HostPool> pool;  // created on first use
     mutable std::mutex pool_mu;
+    uint64_t uid = 0;  // unique among the indexes of the process (a doc set remembers the index it was made for)
     uint32_t num_anchors = 0, doc_lo = 0, doc_hi = 0;
     uint32_t bitmap_base = 0;   // doc id of bit 0 of the list bitmaps: doc_lo rounded down to 65536
     uint64_t bitmap_words = 0;  // words of one list bitmap
@@ -611,6 +612,27 @@ struct Index {
 };
 
 std::unique_ptr<Index> build_index(const IndexBuilder& b, int device);
+
+// ------------------------------------------------------------------ doc sets
+// A caller's id set staged in HBM in the image the scans read for an id-only list — byte for byte what build_index makes of a posting list's ids:
+//   docs      the sorted unique ids inside [doc_lo, doc_hi), padded to a multiple of 4 entries with 0xFFFFFFFF
+//   bitmap    (dense sets: range >= 65536 and local_len * 64 >= range) Index::bitmap_words words, bit (doc - bitmap_base)
+//   rank_dir  (with the bitmap) entries below bitmap_base + (k << kRankShift), k = 0 .. bitmap_words / 16
+//   tile_dir  (range >= 65536 and local_len * 4096 >= range) entries below bitmap_base + (k << kTileDirShift), k = 0 .. bitmap_words / 512 + 3
+// Built on the device (docset.hip) by make_docset, immutable afterwards: any number of requests and threads share one.
+struct DocSet {
+    uint64_t index_uid = 0;  // Index::uid of the index it was made for
+    uint32_t num_anchors = 0, doc_lo = 0, doc_hi = 0;
+    uint64_t len = 0;        // unique ids of the whole set (the same on every shard)
+    uint32_t local_len = 0;  // those inside [doc_lo, doc_hi)
+    uint64_t bitmap_words = 0, rank_entries = 0, tile_entries = 0;  // elements of the parts the set carries (0: none)
+    DevBuf docs, bitmap, rank_dir, tile_dir;
+    uint64_t device_bytes = 0;
+    float ms_mark = -1.0f, ms_count_scan = -1.0f, ms_expand = -1.0f;  // VQ_DOCSET_TIMING=1: HIP event times of the three stages of its construction
+};
+// ids: n anchor ids in any order, duplicates allowed, in host memory or (on_device) in the index's GPU's memory.  Synchronous.  An id >= num_anchors:
+// ERR_INVALID_ARGUMENT, with their number in the message
+std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids, uint64_t n, bool on_device);
 
 // ------------------------------------------------------------------ compiled query
 struct HList {
@@ -677,6 +699,7 @@ struct CompiledQuery {
     // request.why_found with request.select (search.rs:220-224): textindex path -> all term ids the search matched there (what get_why_found flattens out of
     // term_id_hits_in_field, why_found.rs:24-27); complete_why_found_requests highlights the returned anchors' texts with them
     std::shared_ptr<const WhyFoundPlan> why_found_plan;
+    std::shared_ptr<const DocSet> docset;  // the request's doc set: its lists point into the set's buffers, so the batch keeps it alive too
     std::string error;
     std::vector<RangeJob> range_requests;  // status == kStatusNeedsRanges
     std::vector<UnionJob> union_requests;  // status == kStatusNeedsUnion: jobs to run before compiling again

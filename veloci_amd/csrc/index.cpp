@@ -150,6 +150,8 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
 
     auto idx = std::make_unique<Index>();
     idx->device = device;
+    static std::atomic<uint64_t> next_uid{1};
+    idx->uid = next_uid.fetch_add(1);
     idx->num_anchors = b.num_anchors;
     idx->doc_lo = b.doc_lo;
     idx->doc_hi = b.doc_hi;

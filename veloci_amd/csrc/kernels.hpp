@@ -167,6 +167,20 @@ void launch_text_best(hipStream_t st, const TextRowD* rows, uint32_t n_rows, con
 void launch_text_select(hipStream_t st, const uint32_t* best, uint32_t num_texts, uint32_t n_slots, const uint32_t* top_ns, uint32_t out_stride, uint32_t* out_counts,
                         uint32_t* out_pairs);
 
+// ---- doc sets (docset.hip): a caller's id set -> the image of an id-only list.  meta[0] = ids >= num_anchors, meta[1] = unique ids of the whole set
+// bit `id` of the zeroed scratch bitmap is set for every id < num_anchors (ids: device memory, 4-byte aligned)
+void launch_docset_mark(hipStream_t st, const uint32_t* ids, uint64_t n, uint32_t num_anchors, uint32_t* scratch, unsigned long long* meta);
+// local[j] = scratch word base_word + j with the bits outside [doc_lo, doc_hi) cleared (j < words; bit 0 of local[0] is doc bitmap_base; words and
+// base_word are multiples of 64), block_counts[b] = set bits of local words [16 b, 16 b + 16), meta[1] += set bits of the whole scratch bitmap
+void launch_docset_count(hipStream_t st, const uint32_t* scratch, uint64_t scratch_words, uint64_t base_word, uint64_t words, uint32_t bitmap_base, uint32_t doc_lo,
+                         uint32_t doc_hi, uint32_t* local, uint32_t* block_counts, unsigned long long* meta);
+// rank_dir[0 .. blocks) (block counts, blocks a multiple of 64) -> their exclusive prefix sums in place, rank_dir[blocks] = the total; partials: blocks / 64 words
+void launch_docset_scan(hipStream_t st, uint32_t* rank_dir, uint64_t blocks, uint32_t* partials);
+// tile_dir[k] = rank_dir[min(k << (kTileDirShift - kRankShift), blocks)] for k < entries
+void launch_docset_tiles(hipStream_t st, const uint32_t* rank_dir, uint64_t blocks, uint32_t* tile_dir, uint64_t entries);
+// docs[rank] = every set bit of the local bitmap as a doc id, ascending, then 0xFFFFFFFF up to a multiple of 4 entries
+void launch_docset_expand(hipStream_t st, const uint32_t* local, const uint32_t* rank_dir, uint64_t words, uint32_t bitmap_base, uint32_t* docs);
+
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst
     uint64_t src, dst;

@@ -4,12 +4,17 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "json.hpp"
+
+namespace vq {
+struct DocSet;  // engine.hpp
+}
 
 namespace vqreq {
 
@@ -100,6 +105,10 @@ struct Request {  // src/search/request/mod.rs:15-87
     // internal, never parsed: only hits ranking BELOW this key are returned (~0: no bound) — page p of a deep request (top + skip beyond
     // what one scan ranks) asks for what lies below the last key of page p-1
     uint64_t key_upper = ~0ull;
+    // never parsed, never printed: the doc set attached to the request (vq_request_set_docset).  The request behaves as if its filter were one more
+    // leaf whose hits_ids are the set's ids (and-ed with `filter` when there is one); the request keeps the set alive
+    std::shared_ptr<const vq::DocSet> docset;
+    bool filtered() const { return filter.has_value() || docset != nullptr; }  // "has a filter", wherever the reference asks that of a request
     bool exact_routes_only = false;  // (internal) second run of a request whose speculative route could not be confirmed: no k_scan_probe_or
 };
 

@@ -426,20 +426,38 @@ def shard_step_end(step, stride=10):
     return out
 
 
-def search_shards_local(shards, requests):
+def search_shards_local(shards, requests, docsets=None):
     """Every doc-range shard in THIS process (tests, single-GPU rehearsals): partial per shard -> exchange_local -> merge, deep requests paged
-    like ShardedSearcher.search_batch pages them."""
-    from .search import PartialBatch, complete_deep_pages, _as_request
+    like ShardedSearcher.search_batch pages them.  docsets[s][i]: the DocSet of request i made on shard s, or None (a doc set belongs to one
+    index, so a request restricted to a set is sent to every shard with that shard's own set)."""
+    from .search import PartialBatch, Request, complete_deep_pages, _as_request
+
+    class PerShard(Request):  # request i as its shards see it: one parsed copy per shard, each with that shard's doc set
+        def __init__(self, per_shard):
+            self.per_shard, self.h, self.has_facets = per_shard, None, per_shard[0].has_facets
+
+        def page_after(self, score, doc_id):
+            return PerShard([r.page_after(score, doc_id) for r in self.per_shard])
+
+        def top_skip(self):
+            return self.per_shard[0].top_skip()
 
     def one_round(reqs, raise_on_error=False):
-        pbs = [PartialBatch(s, reqs) for s in shards]
+        pbs = [PartialBatch(s, [r.per_shard[k] if isinstance(r, PerShard) else r for r in reqs]) for k, s in enumerate(shards)]
         g = exchange_local(pbs)
         res = pbs[0].merge(g.data_ptr(), len(shards), raise_on_error=raise_on_error)
         for pb in pbs[1:]:
             pb.merge(None, 1, raise_on_error=False)  # releases the shard's workspace
         return res
 
-    requests = [_as_request(r) for r in requests]
+    if docsets is None:
+        requests = [_as_request(r) for r in requests]
+    else:
+        if len(docsets) != len(shards) or any(len(d) != len(requests) for d in docsets):
+            raise ValueError("docsets: one list per shard with one entry (a DocSet or None) per request")
+        if any(isinstance(r, Request) for r in requests):
+            raise ValueError("docsets: the requests must be given as JSON or dicts (every shard parses its own copy)")
+        requests = [PerShard([Request(r, docsets[k][i]) for k in range(len(shards))]) for i, r in enumerate(requests)]
     results = one_round(requests, raise_on_error=True)
     if any(getattr(r, "is_page", False) for r in results):
         results = complete_deep_pages(requests, results, one_round)

@@ -43,10 +43,94 @@ class SearchResult:
         return f"SearchResult(num_hits={self.num_hits}, data={self.data[:3]}..., facets={self.facets})"
 
 
-class Request:
-    """A parsed search::Request (`vq_request`).  Accepts the reference's JSON (str/bytes) or a dict."""
+class DocSet:
+    """A set of anchor ids staged on the index's GPU (`vq_docset`).  Attached to a request it restricts the search to the set's docs, exactly as
+    a `filter` leaf whose hits are these ids would (and-ed with the request's own `filter`).  `ids`: a numpy array or sequence of non-negative
+    ints (copied as uint32; any order, duplicates allowed), or a contiguous torch tensor of dtype int32 / uint32 on the index's device (read in
+    place, no host copy).  Immutable; any number of requests may share one, and a request keeps its set alive after `close()`."""
 
-    def __init__(self, request):
+    def __init__(self, index, ids):
+        self.L = _lib.lib()
+        self.h = None
+        on_device, keep = 0, None
+        if type(ids).__module__.split(".")[0] == "torch":
+            import torch
+            if ids.dtype not in (torch.int32, torch.uint32) or not ids.is_contiguous() or ids.dim() != 1:
+                raise ValueError("DocSet: a torch tensor of ids must be one-dimensional, contiguous and of dtype int32 or uint32")
+            if ids.is_cuda:
+                if ids.device.index != index.device:
+                    raise ValueError("DocSet: the ids tensor is not on the index's device")
+                torch.cuda.current_stream(ids.device).synchronize()  # the library reads the ids on a stream of its own
+                on_device, keep, ptr, n = 1, ids, ids.data_ptr(), ids.numel()
+            else:
+                ids = ids.numpy()
+        if not on_device:
+            arr = np.asarray(ids)
+            if arr.size and arr.dtype.kind not in "iu":
+                raise ValueError("DocSet: ids must be integers")
+            if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 0xFFFFFFFF):
+                raise ValueError("DocSet: ids must fit an unsigned 32-bit integer")
+            keep = np.ascontiguousarray(arr.reshape(-1), dtype=np.uint32)
+            ptr, n = keep.ctypes.data, keep.size
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_create(index.h, C.c_void_p(ptr) if n else None, n, on_device, C.byref(h)))
+        self.h = h
+        del keep
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("DocSet: used after close()")
+        return self.h
+
+    def __len__(self):
+        """unique ids of the whole set (the same on every shard)"""
+        return int(self.L.vq_docset_len(self._handle()))
+
+    @property
+    def local_len(self):
+        """those inside the index's doc range"""
+        return int(self.L.vq_docset_local_len(self._handle()))
+
+    @property
+    def device_bytes(self):
+        return int(self.L.vq_docset_device_bytes(self._handle()))
+
+    def part(self, which):
+        """vq_debug_docset_part: 0 the local ids, 1 bitmap words, 2 rank directory, 3 tile directory, 4 the local ids with their padding (numpy uint32;
+        empty when the set carries no such part)"""
+        n = int(self.L.vq_debug_docset_part(self._handle(), which, None, 0))
+        out = np.zeros(n, np.uint32)
+        if n:
+            self.L.vq_debug_docset_part(self._handle(), which, out.ctypes.data_as(C.c_void_p), n)
+        return out
+
+    def ids(self):
+        """the set's ids inside the index's doc range, sorted and unique (numpy uint32)"""
+        return self.part(0)
+
+    def timings(self):
+        """(mark, count + scan, expand) in ms, recorded when the set was made with VQ_DOCSET_TIMING=1 in the environment; else None"""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        if self.L.vq_debug_docset_timings(self._handle(), C.byref(a), C.byref(b), C.byref(c)) != 0:
+            return None
+        return a.value, b.value, c.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vq_docset_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Request:
+    """A parsed search::Request (`vq_request`).  Accepts the reference's JSON (str/bytes) or a dict; `docset`: a DocSet to attach."""
+
+    def __init__(self, request, docset=None):
         if isinstance(request, dict):
             request = json.dumps(request)
         if isinstance(request, str):
@@ -56,6 +140,16 @@ class Request:
         _lib.check(self.L.vq_request_parse(request, len(request), C.byref(h)))
         self.h = h
         self.has_facets = bool(self.L.vq_request_has_facets(self.h))  # from the PARSED request: decides the exchange path of a sharded step on every rank alike
+        if docset is not None:
+            self.set_docset(docset)
+
+    def set_docset(self, docset):
+        """Attach `docset` (None detaches) — `vq_request_set_docset`.  The request keeps the set alive; its JSON rendering does not change."""
+        _lib.check(self.L.vq_request_set_docset(self.h, docset._handle() if docset is not None else None))
+
+    def to_json(self):
+        """`vq_request_to_json`: what the parser understood."""
+        return self.L.vq_request_to_json(self.h).decode()
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -149,14 +243,27 @@ def _take_result(L, h):
         L.vq_result_free(h)
 
 
-def _as_request(r):
-    return r if isinstance(r, Request) else Request(r)
+def _as_request(r, docset=None):
+    """(a Request object handed in with a doc set has the set attached to it, as by set_docset)"""
+    if not isinstance(r, Request):
+        return Request(r, docset)
+    if docset is not None:
+        r.set_docset(docset)
+    return r
 
 
-def search(request, index):
-    """== veloci::search::search(request, &persistence) (src/search.rs:143-228)."""
+def _with_docsets(requests, docsets):
+    if docsets is None:
+        return [_as_request(r) for r in requests]
+    if len(docsets) != len(requests):
+        raise ValueError("docsets: one entry (a DocSet or None) per request")
+    return [_as_request(r, d) for r, d in zip(requests, docsets)]
+
+
+def search(request, index, docset=None):
+    """== veloci::search::search(request, &persistence) (src/search.rs:143-228); `docset`: restrict the search to a DocSet's ids."""
     L = _lib.lib()
-    req = _as_request(request)
+    req = _as_request(request, docset)
     out = C.c_void_p()
     _lib.check(L.vq_search(index.h, req.h, C.byref(out)))
     return _take_result(L, out)
@@ -260,10 +367,10 @@ def _entry_batch(entry, requests, index, raise_on_error):
     return results
 
 
-def search_batch(requests, index, raise_on_error=True):
-    """n independent searches executed as one device batch (`vq_search_batch`)."""
+def search_batch(requests, index, raise_on_error=True, docsets=None):
+    """n independent searches executed as one device batch (`vq_search_batch`); `docsets`: one DocSet or None per request."""
     L = _lib.lib()
-    reqs = [_as_request(r) for r in requests]
+    reqs = _with_docsets(requests, docsets)
     n = len(reqs)
     arr = (C.c_void_p * n)(*[r.h for r in reqs])
     outs = (C.c_void_p * n)()
@@ -286,8 +393,8 @@ def search_batch(requests, index, raise_on_error=True):
 class RequestBatch:
     """n parsed requests as one C array: build once, search many times (the throughput path)."""
 
-    def __init__(self, requests):
-        self.reqs = [_as_request(r) for r in requests]
+    def __init__(self, requests, docsets=None):
+        self.reqs = _with_docsets(requests, docsets)
         self.n = len(self.reqs)
         self.arr = (C.c_void_p * self.n)(*[r.h for r in self.reqs])
         self.has_facets = any(getattr(r, "has_facets", True) for r in self.reqs)
@@ -302,11 +409,14 @@ class RequestBatch:
         return self._splits[k]
 
 
-def search_batch_flat(batch, index, stride=10):
-    """`vq_search_batch_flat`: returns (num_hits u64[n], counts u32[n], ids u32[n, stride], scores f32[n, stride], status i32[n])."""
+def search_batch_flat(batch, index, stride=10, docsets=None):
+    """`vq_search_batch_flat`: returns (num_hits u64[n], counts u32[n], ids u32[n, stride], scores f32[n, stride], status i32[n]).
+    `docsets`: one DocSet or None per request."""
     L = _lib.lib()
     if not isinstance(batch, RequestBatch):
-        batch = RequestBatch(batch)
+        batch = RequestBatch(batch, docsets)
+    elif docsets is not None:
+        _with_docsets(batch.reqs, docsets)
     n = batch.n
     num_hits = np.zeros(n, np.uint64)
     counts = np.zeros(n, np.uint32)

@@ -294,6 +294,24 @@ uint32_t vq_debug_probe_occupancy(uint32_t shape, uint32_t nd, uint32_t na, uint
     if (lds_bytes) *lds_bytes = uint32_t(lds);
     return vq::debug_probe_occupancy(shape, lds);
 }
+/* tests (like the accessor above: exported, not part of the header): list `token` of a posting store as the probe kernels' 16-bit array image —
+   per 32768-doc tile its entries, in-tile offset << 1 | low score class, padded to a multiple of 8 with 0xFFFF — and the list's raw f16 pivot and
+   maximum (pivot == maximum: the list has no class).  -> entries of the image (`out` takes up to `cap` of them); 0: the list has no such image */
+uint64_t vq_debug_arr16_list(const vq_index* index, const char* store_path, uint32_t token, uint16_t* out, uint64_t cap, uint16_t* pivot_raw, uint16_t* max_raw) {
+    if (!index || !store_path) return 0;
+    auto it = index->idx->postings.find(store_path);
+    if (it == index->idx->postings.end()) return 0;
+    const PostingStore& ps = it->second;
+    if (token >= ps.num_tokens || ps.ak_start.empty() || ps.ak_start[token] < 0) return 0;
+    const uint64_t ptiles = (index->idx->bitmap_words >> (kProbeTileShift - 5)) + 2;  // (the list's directory ends with the granules below that tile: all of them)
+    uint32_t gran = 0;
+    if (hipMemcpy(&gran, ps.gdir.as<uint32_t>() + ps.gd_start[token] + ptiles, 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    const uint64_t n = uint64_t(gran) * 8, take = std::min(n, cap);
+    if (take && out && hipMemcpy(out, ps.arr16.as<uint16_t>() + uint64_t(ps.ak_start[token]) * 8, take * 2, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (pivot_raw) *pivot_raw = ps.pivot_raw[token];
+    if (max_raw) *max_raw = ps.max_raw[token];
+    return n;
+}
 /* tests, tools: requests that ran a second time because a speculative route's result could not be confirmed (k_scan_probe_or) */
 uint64_t vq_index_speculative_reruns(const vq_index* index) { return index ? index->idx->or_reruns.load() : 0; }
 /* tests, tools: since the index was built, the probes of suggest batches that k_dict_topn answered and the match records those batches copied back

@@ -759,6 +759,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             h.flags = LIST_HAS_SCORES;
             h.term_score = e.score;
             h.max_raw = ps.max_raw[e.tid];
+            h.pivot_raw = ps.pivot_raw[e.tid];
             if (!ps.bm_start.empty() && ps.bm_start[e.tid] >= 0) {
                 h.flags |= LIST_BITMAP;
                 h.d_bitmap = ps.bitmaps.as<uint32_t>() + ps.bm_start[e.tid];

@@ -26,6 +26,14 @@ constexpr int kMaxOps = 160;
 constexpr int kMaxSkipWhen = 4;
 constexpr uint32_t kTileDirShift = 14;  // tile directory of an id list: one entry per 16384 docs (the tile of k_scan_simple)
 constexpr uint32_t kProbeTileShift = 15;  // the tile of k_scan_probe: 32768 docs = every second directory entry
+// An arr16 entry is (doc - tile_lo) << 1 | low: 15 bits of in-tile offset and the posting's score class.  A pad is 0xFFFF, the largest value;
+// the one real entry that could equal it (offset 32767 in the low class) is written without the bit.
+static_assert(kProbeTileShift == 15, "an arr16 entry holds a 15-bit in-tile offset and a class bit");
+constexpr uint32_t kArrPadRel = (1u << kProbeTileShift) - 1u;
+#ifndef VQ_SCORE_CLASS_DIV  // experiment builds (make variant DEFS=-DVQ_SCORE_CLASS_DIV=4): the share of a list above its pivot
+#define VQ_SCORE_CLASS_DIV 8
+#endif
+constexpr uint32_t kScoreClassDiv = VQ_SCORE_CLASS_DIV;  // the top 1/8 of an array list's scores lie above its pivot (profiles/score_class/README.md)
 constexpr uint32_t kRankShift = 9;  // rank directory of a dense list: one entry per 512 docs (16 bitmap words = one 64-byte sector)
 
 enum ListFlags : uint32_t {
@@ -42,7 +50,7 @@ struct DList {  // 56 B
     uint32_t flags;
     float term_score;        // s_t (search_field.rs:426), request.boost folded in (:359-364)
     uint16_t max_raw;        // largest f16 bit pattern among the list's scores (all non-negative): bounds every posting value of the list
-    uint16_t pad;
+    uint16_t pivot_raw;      // array lists (DProbeLeaf::arr16): entries with the low bit set have a raw score <= this; == max_raw: the list has no such class
     const uint32_t* bitmap;    // LIST_BITMAP: bit (doc - bitmap_base) set for every doc of the list
     const uint32_t* rank_dir;  // LIST_BITMAP: entries of the list below doc bitmap_base + (k << kRankShift)
     const uint32_t* tile_dir;  // lists of at least 1/4096 of the shard's docs (null otherwise): entries below doc bitmap_base + (k << kTileDirShift)
@@ -236,7 +244,7 @@ __host__ __device__ inline bool sf_union_packed(uint32_t f) { return (f & kSfUni
 // postings grouped by 32768-doc tile, every tile padded to a multiple of 8 entries (a granule) with all-ones entries.
 struct DProbeLeaf {
     const uint32_t* cov32;  // (doc - tile_lo) << 16 | f16 score: what the cover streams; an array operand's scores are gathered from here
-    const uint16_t* arr16;  // doc - tile_lo, same indexing (null: some tile holds more than 2048 entries)
+    const uint16_t* arr16;  // (doc - tile_lo) << 1 | low score class (kArrPadRel), same indexing (null: some tile holds more than 2048 entries)
     const uint32_t* gdir;   // granules below tile k (tile 0 starts at QHeader::bitmap_base)
 };
 struct DProbe {

@@ -360,6 +360,7 @@ struct PostingStore {  // "<field>.textindex.to_anchor_id_score": padded segment
     std::vector<uint32_t> len;          // entries of list t inside this shard
     std::vector<uint64_t> global_len;   // entries of list t in the unsharded index
     std::vector<uint16_t> max_raw;      // largest f16 score bits of list t (upper bound for OR pruning)
+    std::vector<uint16_t> pivot_raw;    // array lists: raw scores <= this are the list's low score class (score_class_pivot); == max_raw: no class
     DevBuf docs;                        // u32, lists padded to a multiple of 4 with 0xFFFFFFFF
     DevBuf scores;                      // f16 bits (u16), same indexing
     uint64_t total_padded = 0;
@@ -374,12 +375,13 @@ struct PostingStore {  // "<field>.textindex.to_anchor_id_score": padded segment
     DevBuf tile_dir;
     // ... and a tile-packed image for k_scan_probe (round 4): the list's postings grouped by 32768-doc tile, every tile padded to a
     // multiple of 8 entries (a "granule"), as `cov32` = (doc - tile_lo) << 16 | f16 score (what a COVER streams: 4 B per posting, one
-    // 16 B/lane load per 256 postings, no index arithmetic) and — when no tile holds more than 2048 entries — as `arr16` = doc - tile_lo
+    // 16 B/lane load per 256 postings, no index arithmetic) and — when no tile holds more than 2048 entries — as `arr16` = (doc - tile_lo) << 1 | score class
     // (what an OPERAND of fewer than 1/16 of the docs is probed in: a sorted 16-bit array per tile, Roaring's array container, 2 B per
     // posting instead of a bit per doc).  Both share one directory: gdir[k] = granules below tile k.
     std::vector<int64_t> pk_start;      // granule offset of list t inside `cov32`, or -1
     std::vector<int64_t> ak_start;      // granule offset of list t inside `arr16`, or -1 (a tile with more than 2048 entries)
     std::vector<int64_t> gd_start;      // entry offset of list t inside `gdir`
+    // An arr16 entry is (doc - tile_lo) << 1 | low (device_types.hpp: kArrPadRel), low = the posting's raw score is <= pivot_raw[t].
     std::vector<uint32_t> tile_most;    // most granules list t has in one tile (0 without a tile-packed image): sizes an array operand's LDS slot per launch
     DevBuf cov32, arr16, gdir;
 };
@@ -642,6 +644,7 @@ struct HList {
     uint32_t flags = 0;
     float term_score = 0.f;
     uint16_t max_raw = 0x7C00;  // +inf: no bound known
+    uint16_t pivot_raw = 0x7C00;  // PostingStore::pivot_raw (== max_raw: the list has no score class)
     float max_value = std::numeric_limits<float>::infinity();  // LIST_F32 (materialised leaf): its largest value
     uint64_t global_len = 0;
     const uint32_t* d_bitmap = nullptr;

@@ -15,6 +15,22 @@
 
 namespace vq {
 
+// Pivot of an array list's score class (PostingStore::pivot_raw): the largest raw score r of the list that at least len / kScoreClassDiv
+// (rounded up) of its scores lie above — the postings at or below it are the list's "low" class.  Returns max_raw where there is no
+// class: all scores equal, or not all of them finite (the raw order is the value order only for finite non-negative f16).
+uint16_t score_class_pivot(const uint16_t* sc, uint32_t len, uint16_t max_raw) {
+    if (len == 0 || max_raw >= 0x7C00u) return max_raw;
+    std::vector<uint32_t> count(size_t(max_raw) + 1, 0u);
+    for (uint32_t i = 0; i < len; ++i) ++count[sc[i]];
+    const uint64_t need = (uint64_t(len) + kScoreClassDiv - 1) / kScoreClassDiv;
+    uint64_t above = 0;  // scores above r
+    for (uint32_t r = max_raw; r-- > 0;) {
+        above += count[r + 1];
+        if (above >= need && count[r]) return uint16_t(r);
+    }
+    return max_raw;
+}
+
 const char* const TOKENS_TO_TEXT_ID = ".tokens_to_text_id";
 const char* const TO_ANCHOR_ID_SCORE = ".to_anchor_id_score";
 const char* const PHRASE_PAIR_TO_ANCHOR = ".phrase_pair_to_anchor";
@@ -345,6 +361,7 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         ps.ak_start.assign(ps.num_tokens, -1);
         ps.gd_start.assign(ps.num_tokens, -1);
         ps.tile_most.assign(ps.num_tokens, 0);
+        ps.pivot_raw = ps.max_raw;  // (no score class: the pivot is the maximum)
         {
             const uint64_t ptiles = (idx->bitmap_words >> (kProbeTileShift - 5)) + 2;  // (entry `one behind the last tile` included)
             uint64_t cov_gran = 0, arr_gran = 0;
@@ -394,6 +411,11 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
                     const bool as_array = ps.ak_start[t] >= 0;
                     const uint32_t* d = docs.data() + ps.start[t];
                     const uint16_t* sc = scores.data() + ps.start[t];
+                    // score class of an array list: an entry's low bit says that its posting's raw score is <= the list's pivot (the
+                    // kernel then bounds the operand by the pivot's value instead of the list maximum's)
+                    if (as_array) ps.pivot_raw[t] = score_class_pivot(sc, ps.len[t], ps.max_raw[t]);
+                    const uint16_t pivot = ps.pivot_raw[t];
+                    const bool classed = as_array && pivot < ps.max_raw[t];
                     uint32_t* c = cov.data() + uint64_t(ps.pk_start[t]) * 8;
                     uint16_t* a = as_array ? arr.data() + uint64_t(ps.ak_start[t]) * 8 : nullptr;
                     uint64_t w = 0;  // entries written
@@ -403,7 +425,9 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
                         for (; i < ps.len[t] && d[i] < thi; ++i, ++w) {
                             const uint32_t rel = uint32_t(d[i] - tlo);
                             c[w] = rel << 16 | sc[i];
-                            if (a) a[w] = uint16_t(rel);
+                            // rel << 1 | low: the order within the tile stays, a pad (0xFFFF) stays the largest value.  Offset 32767 in the
+                            // low class would BE a pad: that one entry never carries the bit (valid: its bound is only looser)
+                            if (a) a[w] = uint16_t(rel << 1 | ((classed && sc[i] <= pivot && rel != kArrPadRel) ? 1u : 0u));
                         }
                         for (; w % 8; ++w) {
                             c[w] = 0xFFFFFFFFu;

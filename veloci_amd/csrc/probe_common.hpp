@@ -16,7 +16,7 @@ constexpr uint32_t kPTW = kPT / 32;             // bitmap words per tile and den
 constexpr uint32_t kPNV = kPTW / 256;           // 16-byte vectors per lane, tile and dense operand (4)
 constexpr uint32_t kPRk = kPT >> kRankShift;    // rank directory entries per tile and dense operand (64: one per lane)
 // shape words (what only the rare paths need — scoring a flush, recomputing raw_min — lives in LDS, not in registers)
-constexpr uint32_t kShCts = 0, kShTs = 1, kShVmax = 4, kShSrc = 7, kShPrunable = 11, kShScores = 12;  // scores: 3 x u64
+constexpr uint32_t kShCts = 0, kShTs = 1, kShVmax = 4, kShSrc = 7, kShPrunable = 11, kShScores = 12, kShVlow = 18;  // scores: 3 x u64; vlow: 3 words behind them
 
 __device__ __forceinline__ void probe_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
@@ -82,10 +82,14 @@ __device__ __forceinline__ float probe_or_sum(const ProbeShape<ND>& S, float vc,
 // Smallest raw f16 score of a cover posting whose hit can still reach the threshold score `thr_f` (wave-wide 64-ary search over the
 // finite non-negative f16 patterns; the bound is monotone in raw).  0: everything stays live.
 // or_mask != ~0: the OR's bound of a doc that holds the cover and exactly the operands of that mask
+// low_mask (AND): the operands (bit i: operand i) whose posting is known to be of its list's low score class — bounded by vlow, not vmax
 template <uint32_t ND>
-__device__ __forceinline__ uint32_t probe_raw_min(const uint32_t* sh, float thr_f, const uint32_t lane, const uint32_t or_mask = 0xFFFFFFFFu) {
+__device__ __forceinline__ uint32_t probe_raw_min(const uint32_t* sh, float thr_f, const uint32_t lane, const uint32_t or_mask = 0xFFFFFFFFu, const uint32_t low_mask = 0u) {
     const ProbeShape<ND> S = probe_shape<ND>(sh);
     if (!S.prunable) return 0u;
+    float vb[ND];
+#pragma unroll
+    for (uint32_t i = 0; i < ND; ++i) vb[i] = ((low_mask >> i) & 1u) ? __uint_as_float(sh[kShVlow + i]) : S.vmax[i];  // (kShVlow: the operand's value at its list's pivot; read only where it is used)
     uint32_t lo = 0u, hi = 0x7C00u;
     while (hi > lo) {  // uniform
         const uint32_t step = (hi - lo + 63u) >> 6;
@@ -93,7 +97,7 @@ __device__ __forceinline__ uint32_t probe_raw_min(const uint32_t* sh, float thr_
         bool dead = false;
         if (p < hi) {
             const float vc = posting_value_fast(S.cts, (uint16_t)p);
-            dead = (or_mask == 0xFFFFFFFFu ? probe_sum<ND>(S, vc, S.vmax) : probe_or_sum<ND>(S, vc, S.vmax, or_mask)) < thr_f;
+            dead = (or_mask == 0xFFFFFFFFu ? probe_sum<ND>(S, vc, vb) : probe_or_sum<ND>(S, vc, vb, or_mask)) < thr_f;
         }  // (p is a finite f16: the short division is exact, tests check all 2^16)  NaN threshold (none yet): never dead
         const uint32_t c = (uint32_t)__popcll(wballot(dead));
         if (c == 0u) hi = lo;

@@ -20,11 +20,16 @@
 // the sum with the cover's value known and every other operand at its list maximum (DList::max_raw) bounds the score from
 // above — f32 add and mul are monotone — and that bound is monotone in the cover's raw f16 score, so the test per posting is one
 // integer compare against `raw_min`, recomputed whenever the threshold moves.  Pruned hits are still counted (num_hits is exact).
+// An ARRAY operand says one bit more: an entry of its 16-bit array is in-tile offset << 1 | low, low = the posting's raw score is at most
+// the list's pivot (DList::pivot_raw: the top eighth of the list's scores lie above it; index.cpp).  The search ends on the hit's entry,
+// so the bit is there when the hit's bound is taken, and a low-class operand counts with the pivot's value instead of the list
+// maximum's: one `raw_min` per set of low-class array operands (rmin[1 << NA]), the same choice again in the flush's re-bound.  Never
+// wrong, only less useful: a list of equal scores has no class (pivot == maximum, no bit set) and is bounded as before.
 //
 // Hits that stay live need their index in every operand (the f16 score is scores[index]): in a bitmap operand the rank directory entry
 // of the doc's 512-doc group (staged in LDS with the tile) + popcount of the group's words below the doc; in an array operand the
-// position the search found (the score is the low half of cov32 at the same position).  Ranked hits are queued and scored 64 at a
-// time, all score gathers of a flush in flight together.
+// position the search found (the score is the low half of cov32 at the same position; the queued index is even, its bit 0 carries the
+// posting's class to the flush).  Ranked hits are queued and scored 64 at a time, all score gathers of a flush in flight together.
 // Same results as k_scan_simple / k_tile_scan bit for bit (tests run every such query through all three).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -124,11 +129,9 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
 
     // ---- the query's shape: the cover leaf streams its tile-packed postings, the others are read as bitmap words or 16-bit arrays
     const uint32_t* ccov = nullptr;
-    const uint32_t* cgdir = nullptr;
     const uint32_t* d_bitmap[NB1];
     const uint32_t* d_rank[NB1];
     const uint16_t* d_arr[NA1];
-    const uint32_t* d_agd[NA1];
     {
         const uint32_t ck = (uint32_t)__ffs((int)sf_cover_mask(sflags)) - 1u;
         const uint32_t am = sf_array_mask(sflags);  // leaf k is an array operand (the host instantiates NA = their number)
@@ -139,7 +142,6 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             const VQ_CONST DList& d = gl[gops[k].list_begin];
             if (k == ck) {
                 ccov = P->leaf[k].cov32;
-                cgdir = P->leaf[k].gdir;
                 if (lane == 0) {
                     sh[kShCts] = __float_as_uint(d.term_score);
                     sh[kShPrunable] = (d.term_score > 0.0f && d.max_raw < 0x7C00u) ? 1u : 0u;
@@ -155,14 +157,15 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
                     }
 #pragma unroll
                 for (uint32_t a = 0; a < NA; ++a)
-                    if (is_arr && NB + a == role) {
-                        d_arr[a] = P->leaf[k].arr16;
-                        d_agd[a] = P->leaf[k].gdir;
-                    }
+                    if (is_arr && NB + a == role) d_arr[a] = P->leaf[k].arr16;
                 if (lane == 0) {
                     const uint16_t mr = d.max_raw;
                     sh[kShTs + role] = __float_as_uint(d.term_score);
-                    sh[kShVmax + role] = (d.term_score > 0.0f && mr < 0x7C00u) ? __float_as_uint(posting_value(d.term_score, mr)) : 0x7F800000u;  // +inf: no bound
+                    const bool bounded = d.term_score > 0.0f && mr < 0x7C00u;
+                    const uint32_t vmax_bits = bounded ? __float_as_uint(posting_value(d.term_score, mr)) : 0x7F800000u;  // +inf: no bound
+                    sh[kShVmax + role] = vmax_bits;
+                    // an array operand's low score class (entries with the low bit: raw <= pivot_raw) is bounded by the pivot's value
+                    sh[kShVlow + role] = (bounded && is_arr && d.pivot_raw < mr) ? __float_as_uint(posting_value(d.term_score, d.pivot_raw)) : vmax_bits;
                     // where the operand's f16 scores are gathered from, as a u16 array: the list's own scores by posting index, or the low
                     // halves of its tile-packed words by (2 x) packed position
                     reinterpret_cast<unsigned long long*>(sh + kShScores)[role] = is_arr ? (unsigned long long)(uintptr_t)P->leaf[k].cov32 : (unsigned long long)(uintptr_t)d.scores;
@@ -194,15 +197,17 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
     }
     __syncthreads();
     unsigned long long thr_seen = *thr;
-    // the smallest raw cover score that can still reach the threshold: one for an AND, one per set of present operands for an OR
-    uint32_t raw_min = 0u;
-    constexpr uint32_t kMasks = OR ? (1u << ND) : 1u;
+    // the smallest raw cover score that can still reach the threshold: for an OR one per set of present operands, for an AND one per set of
+    // array operands whose posting is of the low score class (the class bits of the entries the searches end on; without arrays: one)
+    constexpr uint32_t kMasks = OR ? (1u << ND) : (1u << NA);
     uint32_t rmin[kMasks];
     auto take_raw_min = [&](const float thr_f) {
-        if (OR) {
 #pragma unroll
-            for (uint32_t m = 0; m < kMasks; ++m) rmin[m] = probe_raw_min<ND>(sh, thr_f, lane, m);
-        } else raw_min = probe_raw_min<ND>(sh, thr_f, lane);
+        for (uint32_t m = 0; m < kMasks; ++m) {
+            const uint32_t r = OR ? probe_raw_min<ND>(sh, thr_f, lane, m) : probe_raw_min<ND>(sh, thr_f, lane, 0xFFFFFFFFu, m << NB);
+            if (!OR && NA) probe_lds_fence();  // (one bound's shape words at a time)
+            rmin[m] = (!OR && NA) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r) : r;  // (uniform: the array shapes' bounds stay out of the vector registers, which <2, 1> has none to spare of)
+        }
     };
     take_raw_min(__uint_as_float(unorder_f32((uint32_t)(thr_seen >> 32))));
 
@@ -218,11 +223,26 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
     const uint32_t t_first = (span_lo - bitmap_base) >> kProbeTileShift;
     const uint32_t t_end = span_hi > span_lo ? ((span_hi - 1u - bitmap_base) >> kProbeTileShift) + 1u : t_first;  // one behind the last tile
     uint32_t dir_base = t_first;
-    auto load_dir = [&](const uint32_t* g) { return as_global(g)[dir_base + lane < t_end ? dir_base + lane : t_end]; };  // (entry t_end exists: one behind the last tile)
-    uint32_t dirv = load_dir(cgdir);
+    // The directories' addresses are looked up in the blob where a slice is loaded — once per 62 tiles —, through a pointer the compiler
+    // cannot see through: kept across the tile loop they would take registers that the array shapes do not have (<2, 1> sits at 128).
+    auto load_dir = [&](const uint32_t which) {  // 0: the cover's directory, 1 + a: array operand a's
+        const uint8_t* b = blob;
+        asm volatile("" : "+s"(b));
+        const VQ_CONST QHeader* Hb = as_const<QHeader>(b);
+        const uint32_t sf = Hb->simple_flags;
+        uint32_t k = (uint32_t)__ffs((int)sf_cover_mask(sf)) - 1u;
+        if (which) {  // uniform: the which-th array leaf, in leaf order (the order the roles were given in)
+            uint32_t am = sf_array_mask(sf);
+            for (uint32_t a = 1; a < which; ++a) am &= am - 1u;
+            k = (uint32_t)__ffs((int)am) - 1u;
+        }
+        const uint32_t* g = as_const<DProbe>(b + Hb->off_simple2)->leaf[k].gdir;
+        return as_global(g)[dir_base + lane < t_end ? dir_base + lane : t_end];  // (entry t_end exists: one behind the last tile)
+    };
+    uint32_t dirv = load_dir(0u);
     uint32_t adv[NA1];
 #pragma unroll
-    for (uint32_t a = 0; a < NA; ++a) adv[a] = load_dir(d_agd[a]);
+    for (uint32_t a = 0; a < NA; ++a) adv[a] = load_dir(1u + a);
     auto dir_at = [&](const uint32_t v, const uint32_t tt) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)(tt - dir_base)); };
 
     // registers of the tile in flight: its words / array vectors and rank entries, its cover postings (the first kPMaxR rounds)
@@ -335,10 +355,17 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
                     f_vd[i] = posting_value(S.ts[i], f_r);
                     if (i + 1u < ND) {  // hits that can no longer reach the threshold drop out, the next operand's gather goes out
                         constexpr uint32_t zero = 0;
-                        f_alive = f_alive && !(sum_of(S, f_vc, f_vd, f_mask) < thr_f);
+                        const uint32_t nx = i + 1u < ND ? i + 1u : zero;  // the next operand (a constant once the loop is unrolled)
+                        // an array operand still to come is bounded by its posting's score class (bit 0 of its index: rank_some): the low
+                        // class by the pivot's value.  (Taken from the index here, not kept per lane across the tiles: f_vd[] of an operand
+                        // still to come is a uniform value)
+                        float vb[ND];
+#pragma unroll
+                        for (uint32_t j = 0; j < ND; ++j) vb[j] = (j > i && j >= NB && (f_idx[j] & 1u)) ? __uint_as_float(sh[kShVlow + j]) : f_vd[j];
+                        f_alive = f_alive && !(sum_of(S, f_vc, vb, f_mask) < thr_f);
                         if (stat && lane == 0) *stat += 2u * (uint32_t)__popcll(wballot(f_alive));
-                        gp = sptr[i + 1u < ND ? i + 1u : zero];
-                        gidx = (f_alive && (!OR || ((f_mask >> (i + 1u < ND ? i + 1u : zero)) & 1u))) ? f_idx[i + 1u < ND ? i + 1u : zero] : 0u;
+                        gp = sptr[nx];
+                        gidx = (f_alive && (!OR || ((f_mask >> nx) & 1u))) ? (nx >= NB ? f_idx[nx] & ~1u : f_idx[nx]) : 0u;
                         last = false;
                     }
                 }
@@ -365,7 +392,7 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
 #pragma unroll
             for (uint32_t i = 0; i < ND; ++i) f_vd[i] = __uint_as_float(sh[kShVmax + i]);
             if (stat && lane == 0) *stat += 2u * count;  // gathered bytes of the span
-            gidx = (f_alive && (!OR || (f_mask & 1u))) ? f_idx[0] : 0u;
+            gidx = (f_alive && (!OR || (f_mask & 1u))) ? (NB ? f_idx[0] : f_idx[0] & ~1u) : 0u;
             f_stage = 1u;
             rhead = (rhead + count) & (kPR - 1u);
             rn -= count;
@@ -386,7 +413,8 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
 #pragma unroll
         for (uint32_t i = 0; i < ND; ++i) {
             const uint16_t* sp = reinterpret_cast<const uint16_t*>((uintptr_t) reinterpret_cast<const unsigned long long*>(sh + kShScores)[i]);
-            const uint32_t ix = rq[(2u + i) * kPR + slot];
+            uint32_t ix = rq[(2u + i) * kPR + slot];
+            if (!OR && i >= NB) ix &= ~1u;  // (an array operand's index carries its posting's score class in bit 0)
             if (ix != 0xFFFFFFFFu) mask |= 1u << i;
             vd[i] = posting_value(S.ts[i], as_global(sp)[(OR && ix == 0xFFFFFFFFu) ? 0u : ix]);
         }
@@ -455,40 +483,57 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             uint32_t e = 0xFFFFFFFFu, pos[NA1];
             bool found = lane < cnt;
             if (found) e = uqe[lane];
-            const uint32_t rel = e >> 16;
+            // an entry is offset << 1 | class: the last entry <= offset * 2 + 1 is the doc's, if it is there.  (Offset 32767: its entry never
+            // carries the class bit, and 0xFFFF is a pad.)  The key takes the offset's place in the high half of `e`, once per round: the
+            // search compares against that half as it did against the offset, and no register is added to the loop
+            {
+                const uint32_t off = e >> 16;
+                e = (off * 2u + 1u < 0xFFFEu ? off * 2u + 1u : 0xFFFEu) << 16 | (e & 0xFFFFu);
+                asm volatile("" : "+v"(e));  // (the offset is e >> 17 from here on: the compiler does not keep the old one)
+            }
 #pragma unroll
             for (uint32_t a = 0; a < NA; ++a) {
                 const uint16_t* A = reinterpret_cast<const uint16_t*>(arr + a * arr_slot);
                 uint32_t lo = 0u, len = a_cnt[a];  // uniform length: every lane takes the same number of steps
 #ifdef VQ_PROBE_NO_SEARCH  // diagnostic build (wrong results): what the kernel takes without the lookups' dependent reads
-                lo = rel & 7u;
+                lo = (e >> 17) & 7u;
                 len = 0u;
 #endif
                 while (len > 1u) {
                     const uint32_t half = len >> 1;
-                    lo = (uint32_t)A[lo + half] <= rel ? lo + half : lo;  // the last entry <= rel
+                    lo = (uint32_t)A[lo + half] <= (e >> 16) ? lo + half : lo;  // the last entry <= the key
                     len -= half;
                 }
 #ifdef VQ_PROBE_NO_SEARCH
-                found = found && a_cnt[a] != 0u && ((uint32_t)A[lo] ^ rel) < 0x2000u;  // (one read; about a quarter of the candidates "found", as in the real query)
+                const uint32_t ent = A[lo];
+                found = found && a_cnt[a] != 0u && ((ent >> 1) ^ (e >> 17)) < 0x2000u;  // (one read; about a quarter of the candidates "found", as in the real query)
 #else
-                found = found && a_cnt[a] != 0u && (uint32_t)A[lo] == rel;
+                const uint32_t ent = A[lo];
+                found = found && a_cnt[a] != 0u && (ent >> 1) == (e >> 17);
 #endif
-                pos[a] = lo;
+                pos[a] = lo * 2u | (ent & 1u);  // bit 0: the posting is of its list's low score class
             }
             const unsigned long long fm = wballot(found);
             hits += (unsigned long long)__popcll(fm);
-            const bool live = found && (e & 0xFFFFu) >= raw_min;
+            uint32_t cls = 0u;  // bit a: the doc's posting in array operand a is of the low class — which of the bounds holds for it
+#pragma unroll
+            for (uint32_t a = 0; a < NA; ++a) cls |= (pos[a] & 1u) << a;
+            // live: the cover's raw score reaches the bound of the doc's class mask.  (A low class only raises the bound — rmin[m] >= rmin[0] —,
+            // and plain compares joined as lane masks take no vector register, where a per-lane selected bound would.)
+            bool live = found && (e & 0xFFFFu) >= rmin[0];
+#pragma unroll
+            for (uint32_t m = 1; m < kMasks; ++m) live = live && !(cls == m && (e & 0xFFFFu) < rmin[(!OR && NA) ? m : 0u]);
             const unsigned long long lm = wballot(live);
             if (lm) {  // uniform
                 if (live) {
+                    const uint32_t rel = e >> 17;
                     const uint32_t slot = (rhead + rn + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull))) & (kPR - 1u);
                     rq[slot] = tile_lo + rel;
                     rq[kPR + slot] = e & 0xFFFFu;
 #pragma unroll
                     for (uint32_t i = 0; i < NB; ++i) rq[(2u + i) * kPR + slot] = bitmap_rank(i, rel);
 #pragma unroll
-                    for (uint32_t a = 0; a < NA; ++a) rq[(2u + NB + a) * kPR + slot] = (a_g0[a] * 8u + pos[a]) * 2u;  // (u16 index of the packed word's low half)
+                    for (uint32_t a = 0; a < NA; ++a) rq[(2u + NB + a) * kPR + slot] = a_g0[a] * 16u + pos[a];  // (u16 index of the packed word's low half — even —, the class in bit 0: the flush bounds the operand by it)
                 }
                 rn += (uint32_t)__popcll(lm);
             }
@@ -545,7 +590,7 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
             // (ballots of the plain compares, joined as masks: a ballot of a joined bool costs two more vector instructions)
             const unsigned long long sm = NB ? (wballot(in) & wballot(bit)) : wballot(in);
             if (NA == 0u) {
-                const bool strong = (ee[c] & 0xFFFFu) >= raw_min;
+                const bool strong = (ee[c] & 0xFFFFu) >= rmin[0];
                 hits += (unsigned long long)__popcll(sm);
                 lm[c] = sm & wballot(strong);
                 live[c] = in && bit && strong;
@@ -637,9 +682,9 @@ __device__ __forceinline__ void probe_body(const uint8_t* __restrict__ blob, con
         if (more) {  // uniform
             if (t + 2u - dir_base >= 64u) {  // the directory slices are used up (62 tiles): the next ones (a wait, once per 62 tiles)
                 dir_base = t + 1u;
-                dirv = load_dir(cgdir);
+                dirv = load_dir(0u);
 #pragma unroll
-                for (uint32_t a = 0; a < NA; ++a) adv[a] = load_dir(d_agd[a]);
+                for (uint32_t a = 0; a < NA; ++a) adv[a] = load_dir(1u + a);
             }
             ng0 = dir_at(dirv, t + 1u);
             ng1 = dir_at(dirv, t + 2u);

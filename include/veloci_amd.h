@@ -431,7 +431,7 @@ int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const 
  * writes the best min(top, non-zero counts) entries, returns their number, -1 on failure. */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts);
 
-/* ---- the pre-pass drivers alone (exec.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs): what a batch runs before its
+/* ---- the pre-pass drivers alone (prepass.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs): what a batch runs before its
  * scans, on jobs the caller describes the way the request compiler does, with every list the drivers build copied back whole.  Jobs are passed as a
  * CSR: job j owns ids[job_off[j] .. job_off[j + 1]) (job_off[0] == 0, at most 2^31 ids, n_jobs >= 1) and names its stores by the paths they were
  * loaded under.  Lists come back to back in out_docs / out_val_bits (f32 bit patterns), `out_cap` entries each: job j's out_len[j] entries and the

@@ -32,7 +32,10 @@ hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
     std::memcpy(d, s, n);
     return hipSuccess;
 }
+static std::atomic<long> g_async_calls{0};  // hipMemcpyAsync + hipMemsetAsync calls so far (tests/native/staging_check.cpp: an empty section issues none)
+long vq_stub_async_calls() { return g_async_calls.load(); }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) {
+    ++g_async_calls;
     std::memcpy(d, s, n);
     return hipSuccess;
 }
@@ -41,6 +44,7 @@ hipError_t hipMemset(void* d, int v, size_t n) {
     return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) {
+    ++g_async_calls;
     std::memset(d, v, n);
     return hipSuccess;
 }
@@ -216,7 +220,7 @@ void launch_dict_scan_wide(hipStream_t, uint32_t char_bytes, const DictProbeW*, 
     no_device("k_dict_scan_wide");
 }
 // VQ_STUB_DICT_SCAN=1 (tools/host_profile.py; the pre-pass batch of tests/native/launch_plan_driver.py): exact / prefix probes answered by a plain
-// loop, so that requests with prefix leaves get through compile_batch (exec.cpp) without a GPU.  The sanitizer test leaves it off: there every launcher throws.
+// loop, so that requests with prefix leaves get through compile_batch (exec.cpp; run_fuzzy_probes in prepass.cpp) without a GPU.  The sanitizer test leaves it off: there every launcher throws.
 void launch_dict_scan(hipStream_t, const DictProbe* probes, uint32_t probe_base, uint32_t n_probes, const uint32_t* off, const uint16_t* chars, const uint16_t* low_chars,
                       uint32_t num_terms, uint32_t* out_count, uint32_t out_cap, DictMatch* out) {
     log_launch("k_dict_scan", {probe_base, n_probes, num_terms, out_cap});

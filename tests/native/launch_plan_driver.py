@@ -3,7 +3,7 @@ VQ_STUB_LAUNCH_LOG=<file>): one batch that reaches every scan class — on an un
 through compile, routing, table packing and the launch calls over a "device" whose launches do nothing but write down what they were given
 (tests/native/hip_stub.cpp).  The routing knobs are read once per process, so every environment leg is a run of its own.
 With VQ_LAUNCH_PLAN_BATCH=prepass (and VQ_STUB_DICT_SCAN=1: the stub answers prefix probes with a plain loop) a second batch runs instead, on the
-same corpus: requests that go round the pre-pass loop of compile_batch (exec.cpp) — dictionary scan, union job, count pre-pass — beside plain
+same corpus: requests that go round the pre-pass loop of compile_batch (exec.cpp; the runners it calls are in prepass.cpp) — dictionary scan, union job, count pre-pass — beside plain
 ones that are compiled once."""
 import json
 import os

@@ -1,4 +1,4 @@
-"""Plain restatements of what the pre-pass drivers build (exec.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs), over the
+"""Plain restatements of what the pre-pass drivers build (prepass.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs), over the
 raw arrays an IndexData was filled from.  Loops and numpy float32 only; tests/test_gpu_prepass_lists.py compares every entry of the device lists
 with these, tests/test_prepass_ref_cpu.py pins them against the CPU oracle.
 

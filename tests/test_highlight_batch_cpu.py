@@ -1,7 +1,6 @@
 """The batched highlight (vq_highlight_batch) without a GPU: the host side over the stubbed device layer (tests/native/highlight_batch_driver.py),
 the same under ASan + UBSan as a program of its own (tests/native/highlight_batch_check.cpp), the compiler's resource report of text_rank.hip,
 and the places that must name the new entry points."""
-import glob
 import json
 import os
 import re
@@ -10,6 +9,7 @@ import sys
 
 import pytest
 
+import sanitized
 import test_kernel_resources as KR
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,27 +41,9 @@ def test_batch_on_the_stubbed_device_equals_the_single_parts_and_the_oracle():
 
 
 def test_highlight_batch_under_asan_and_ubsan(tmp_path):
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    host_srcs = re.search(r"^HOST_SRCS = (.*)$", mk, re.M).group(1).split()
-    stubs = sorted(glob.glob(os.path.join(HERE, "native", "hip_stub*.cpp")))
+    host_srcs, stubs = sanitized.host_sources()
     assert any(s.endswith("hip_stub_text_rank.cpp") for s in stubs) and "exec.cpp" in host_srcs
-    exe = str(tmp_path / "highlight_batch_check")
-    objs = []
-    jobs = []
-    for src in [os.path.join(CSRC, s) for s in host_srcs] + stubs + [os.path.join(HERE, "native", "highlight_batch_check.cpp")]:
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        objs.append(obj)
-        jobs.append((src, subprocess.Popen(["g++", "-std=c++17", "-O0", "-g1", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsanitize=address,undefined",
-                                            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
-    for src, p in jobs:
-        _, err = p.communicate(timeout=900)
-        assert p.returncode == 0, (src, err[-3000:])
-    # the sanitizers' runtimes are linked statically: the program then runs in whatever environment the suite runs in, with no library order to keep
-    r = subprocess.run(["g++", "-pthread", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-o", exe, *objs], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ))
-    tail = r.stdout[-2000:] + r.stderr[-4000:]
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error:" not in r.stderr and "LeakSanitizer" not in r.stderr, tail
+    r, tail = sanitized.run(sanitized.build_host_check(tmp_path, "highlight_batch_check", host_srcs, stubs))
     assert r.returncode == 0 and "HIGHLIGHT_BATCH_CHECK_OK " in r.stdout, tail
     stats = json.loads(r.stdout.split("HIGHLIGHT_BATCH_CHECK_OK ", 1)[1])
     print(stats)

@@ -1,4 +1,4 @@
-"""Regex leaves on the device route (veloci_amd/csrc/regex_dfa.cpp, dict_regex.hip, run_fuzzy_probes in exec.cpp) without a GPU: the pattern -> DFA
+"""Regex leaves on the device route (veloci_amd/csrc/regex_dfa.cpp, dict_regex.hip, run_fuzzy_probes in prepass.cpp) without a GPU: the pattern -> DFA
 compiler against std::wregex under ASan + UBSan (tests/native/regex_dfa_check.cpp, a program of its own), the compiler's resource report of
 k_dict_regex, and the whole host side over the stubbed device layer against the host route (tests/native/regex_route_driver.py)."""
 import json
@@ -8,6 +8,7 @@ import sys
 
 import pytest
 
+import sanitized
 import test_kernel_resources as KR
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -16,14 +17,9 @@ CSRC = os.path.join(ROOT, "veloci_amd", "csrc")
 
 
 def test_dfa_agrees_with_std_wregex_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "regex_dfa_check")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-o", exe,
-                        os.path.join(HERE, "native", "regex_dfa_check.cpp"), os.path.join(CSRC, "regex_dfa.cpp")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = sanitized.build(tmp_path, "regex_dfa_check", [os.path.join(HERE, "native", "regex_dfa_check.cpp"), os.path.join(CSRC, "regex_dfa.cpp")], flags=["-O1", "-Wall"])
     # 700 patterns per alphabet (ASCII, Latin-1 + Greek, one above U+FFFF) x 200 terms x ignore_case x starts_with
-    r = subprocess.run([exe, "700", "200"], capture_output=True, text=True, timeout=900)
-    tail = r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error:" not in r.stderr, tail
+    r, tail = sanitized.run(exe, ["700", "200"], timeout=900)
     assert "REGEX_DFA_CHECK " in r.stdout, tail
     stats = json.loads(r.stdout.split("REGEX_DFA_CHECK ", 1)[1])
     print(stats)

@@ -1,4 +1,4 @@
-"""The dense union route (veloci_amd/csrc/union_dense.hip, run_union_jobs in exec.cpp) without a GPU: the compiler's resource report of its
+"""The dense union route (veloci_amd/csrc/union_dense.hip, run_union_jobs in prepass.cpp) without a GPU: the compiler's resource report of its
 kernels, and the host side of wide leaves over the stubbed device layer, plain and under ASan + UBSan (tests/native/union_dense_driver.py)."""
 import json
 import os

@@ -367,7 +367,7 @@ int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t to
     return vq::debug_facet_select(hist, num_values, top, misalign, out_values, out_counts);
 }
 
-/* self-checks (tests): the pre-pass drivers of exec.cpp alone — the jobs described as the compiler describes them, run by run_*_jobs, every
+/* self-checks (tests): the pre-pass drivers of prepass.cpp alone — the jobs described as the compiler describes them, run by run_*_jobs, every
    job's whole (doc, f32) list copied back with its 8 sentinel entries.  0; -1 without a device (or when the driver fails); -2 for arguments
    outside the documented ranges */
 

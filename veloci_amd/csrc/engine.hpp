@@ -6,6 +6,7 @@
 #include <cmath>
 #include <chrono>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <limits>
 #include <memory>
@@ -32,6 +33,14 @@ using vqreq::VelociError;
         hipError_t _e = (expr);                                                                                               \
         if (_e != hipSuccess) throw vqreq::VelociError(vqreq::ERR_DEVICE, std::string("HIP error: ") + hipGetErrorString(_e) + " at " #expr); \
     } while (0)
+
+// small helpers the executor's translation units share (exec.cpp, prepass.cpp)
+inline bool timing_enabled() {
+    static const bool on = std::getenv("VQ_TIMING") != nullptr;
+    return on;
+}
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // suffix constants, reference src/persistence.rs:23-50
 extern const char* const TOKENS_TO_TEXT_ID;

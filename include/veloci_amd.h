@@ -466,6 +466,22 @@ int vq_debug_range_hits(const vq_index*, const char* const* store_paths, const u
 int vq_debug_boost1n_lists(const vq_index*, const char* const* to_parent_paths, const char* const* to_anchor_paths, const char* const* boost_paths,
                            const uint64_t* job_off, const uint32_t* text_ids, uint32_t n_jobs, uint64_t out_cap, uint32_t* out_len, uint32_t* out_total,
                            uint32_t* out_flags, uint32_t* out_docs, uint32_t* out_val_bits);
+/* The count pre-pass alone (k_tile_scan in count mode): the n requests (doc sets attached or not; n >= 1) go through the compilation passes of a
+ * batch up to and including the count pre-pass — dictionary scans and union / locality / range jobs first where a leaf needs them — and no result
+ * scan is launched.  Per request: status[i] = VQ_OK when it was counted, VQ_COUNTS_NONE when it needs no count pre-pass, otherwise the error code
+ * its search would return (the first such text is in vq_last_error; a null request: VQ_ERR_INVALID_ARGUMENT); has_filter[i] (0 / 1) and
+ * filter_count[i], the ids of the filter (the request's `filter` and-ed with its doc set); n_spans[i] / tile_words[i], what the count query was
+ * compiled with (0 for a request that was not counted).  The measured nodes of request i are entries node_off[i] .. node_off[i + 1] of node_ids
+ * (the compiler's preorder number of the node inside search_req: the root is 0, an operand follows its predecessor's whole sub-tree), hits and
+ * hits_in_filter, `out_cap` entries each; node_off takes n + 1 numbers.  hits_in_filter is 0 for a request without a filter (that counter is
+ * never written).  summed == 0: the numbers of this shard as the kernel wrote them; 1: after the
+ * sum over the shards (vq_index_set_allreduce), what the compiler goes by — the same on an unsharded index.  Returns 0; -1 without a device or
+ * when a pre-pass fails; -2 for a null pointer, n == 0, summed outside 0 / 1 or `out_cap` too small for the nodes.  With profiling on the launch
+ * is accounted under "k_tile_scan<count pre-pass>" like a batch's. */
+#define VQ_COUNTS_NONE (-1)
+int vq_debug_node_counts(const vq_index*, const vq_request* const* requests, size_t n, int summed, uint64_t out_cap, int* status, uint32_t* has_filter,
+                         uint64_t* filter_count, uint32_t* n_spans, uint32_t* tile_words, uint64_t* node_off, uint32_t* node_ids, uint64_t* hits,
+                         uint64_t* hits_in_filter);
 
 const char* vq_version(void);
 

@@ -23,7 +23,7 @@ SYMBOLS = [
     "vq_search_batch_partial_at", "vq_partial_slots", "vq_index_partial_arena_ptr", "vq_partial_total_bytes", "vq_merge_partials_flat_strided",
     "vq_comm_unique_id", "vq_comm_init", "vq_comm_init_custom", "vq_comm_destroy", "vq_shard_step_begin", "vq_shard_step_end", "vq_shard_step_free", "vq_shard_step_flat",
     "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_debug_union_lists", "vq_debug_locality_lists",
-    "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_version",
+    "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_version",
     "vq_docset_create", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
     "vq_request_set_docset",
 ]
@@ -136,6 +136,7 @@ def lib():
         "vq_debug_locality_lists": (i, [vp, C.POINTER(cp), C.POINTER(cp), vp, vp, u32, u64, vp, vp, vp]),
         "vq_debug_range_hits": (i, [vp, C.POINTER(cp), vp, vp, vp, vp, u32, vp]),
         "vq_debug_boost1n_lists": (i, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(cp), vp, vp, u32, u64, vp, vp, vp, vp, vp]),
+        "vq_debug_node_counts": (i, [vp, C.POINTER(vp), sz, i, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "vq_merge_partials": (i, [vp, vp, vp, u32, C.POINTER(vp), C.POINTER(i)]),
         "vq_merge_partials_flat": (i, [vp, vp, vp, u32, sz, vp, vp, vp, vp, vp]),
         "vq_partial_free": (None, [vp]),

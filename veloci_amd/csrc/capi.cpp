@@ -1151,6 +1151,48 @@ int vq_search_batch(const vq_index* index, const vq_request* const* requests, si
     });
 }
 
+/* self-check (tests): what the count pre-pass measures for the requests of one batch — the batch's own compilation up to and including
+   run_count_queries (exec.cpp debug_node_counts), no result scan.  Request i's measured nodes are entries node_off[i] .. node_off[i + 1] of
+   node_ids / hits / hits_in_filter, in counter order.  0; -1 without a device (or when a pre-pass fails); -2 for arguments outside the documented
+   ranges (a null pointer, n == 0, `out_cap` too small for the nodes) */
+int vq_debug_node_counts(const vq_index* index, const vq_request* const* requests, size_t n, int summed, uint64_t out_cap, int* status, uint32_t* has_filter,
+                         uint64_t* filter_count, uint32_t* n_spans, uint32_t* tile_words, uint64_t* node_off, uint32_t* node_ids, uint64_t* hits,
+                         uint64_t* hits_in_filter) {
+    if (!index || !n || !requests || summed < 0 || summed > 1 || !status || !has_filter || !filter_count || !n_spans || !tile_words || !node_off ||
+        (out_cap && (!node_ids || !hits || !hits_in_filter)))
+        return -2;
+    try {
+        const std::vector<const Request*> reqs = request_pointers(requests, n);
+        const std::vector<vq::NodeCounts> counts = vq::debug_node_counts(*index->idx, reqs.data(), n, summed != 0);
+        g_err.clear();
+        uint64_t need = 0;
+        for (const vq::NodeCounts& c : counts) need += c.nodes.size();
+        if (need > out_cap) return -2;
+        node_off[0] = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const vq::NodeCounts& c = counts[i];
+            status[i] = c.status;
+            if (c.status > 0 && g_err.empty()) g_err = c.error;  // (the first failing request's text)
+            has_filter[i] = c.has_filter ? 1u : 0u;
+            filter_count[i] = c.filter_count;
+            n_spans[i] = c.n_spans;
+            tile_words[i] = c.tile_words;
+            uint64_t at = node_off[i];
+            for (const vq::NodeCounts::Node& nd : c.nodes) {
+                node_ids[at] = nd.id;
+                hits[at] = nd.hits;
+                hits_in_filter[at] = nd.hits_in_filter;
+                ++at;
+            }
+            node_off[i + 1] = at;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 // Explain records and why_found_info (why_found with select) are produced by vq_search / vq_search_json / vq_search_batch: the flat outputs have no
 // place for them, and on the sharded path a rank only holds the postings and the texts of its own docs.
 static void decline_explain(std::vector<std::unique_ptr<Result>>& results, std::vector<int>& st, std::vector<std::string>& errs, const char* where) {

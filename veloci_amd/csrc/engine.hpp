@@ -781,6 +781,22 @@ void run_range_jobs(const Index& idx, Workspace& ws, RangeTable& table, const Un
 // (VQ_UNION_DENSE_MIN, else 64 x 64)
 void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st, int64_t dense_min = -1);
 void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStream_t)>& body);  // exec.cpp: what vq_debug_*_lists run the drivers in
+// What the count pre-pass measured for one request of a batch (vq_debug_node_counts).  status: 0 = counted, kNodeCountsNone = the request needs no
+// count pre-pass, otherwise the error code its search would return (`error`: the text)
+constexpr int kNodeCountsNone = -1;
+struct NodeCounts {
+    int status = 0;
+    std::string error;
+    bool has_filter = false;
+    uint64_t filter_count = 0;
+    uint32_t n_spans = 0, tile_words = 0;  // what the count query was compiled with
+    struct Node {
+        uint32_t id;  // the compiler's preorder number of the node in search_req
+        uint64_t hits, hits_in_filter;
+    };
+    std::vector<Node> nodes;
+};
+std::vector<NodeCounts> debug_node_counts(const Index& idx, const vqreq::Request* const* reqs, size_t n, bool summed);  // exec.cpp
 struct Result;
 // Deep requests (top + skip > kMaxTopK) of an unsharded batch: results[i] holds page 0; fetch the following pages (each one scan that
 // ranks only keys below the previous page's last) and cut the requested window.

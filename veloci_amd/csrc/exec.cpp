@@ -456,19 +456,19 @@ static void compile_with_jobs(const Index& idx, Workspace& ws, PartialBatch& pb,
     }
 }
 
-// ANDs whose summation order / label follow run-time operand sizes: count pre-pass, then the final compilation
-static void compile_with_counts(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, BatchTables& tables, hipStream_t pst) {
-    std::vector<size_t> need;
+// The count pre-pass of the batch's queries that are one (`need`: their positions) -> their numbers, on a sharded index summed over the shards
+// (`sum` off: as this shard's kernel wrote them — vq_debug_node_counts)
+static std::vector<QueryCounts> measure_counts(const Index& idx, Workspace& ws, PartialBatch& pb, hipStream_t pst, std::vector<size_t>& need, bool sum = true) {
     std::vector<CompiledQuery*> cqs;
     for (size_t i = 0; i < pb.queries.size(); ++i)
         if (pb.queries[i].status == kStatusNeedsCounts) {
             need.push_back(i);
             cqs.push_back(&pb.queries[i]);
         }
-    if (need.empty()) return;
     std::vector<QueryCounts> counts;
+    if (need.empty()) return counts;
     run_count_queries(idx, ws, cqs, counts, pst);
-    if (idx.sharded()) {  // result sizes are sums over the shards
+    if (idx.sharded() && sum) {  // result sizes are sums over the shards
         auto each = [&](auto&& f) {  // every number of the counts, in one order
             for (auto& c : counts) {
                 f(c.filter_count);
@@ -481,6 +481,13 @@ static void compile_with_counts(const Index& idx, Workspace& ws, PartialBatch& p
         size_t k = 0;
         each([&](uint64_t& v) { v = flat[k++]; });
     }
+    return counts;
+}
+
+// ANDs whose summation order / label follow run-time operand sizes: count pre-pass, then the final compilation
+static void compile_with_counts(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, BatchTables& tables, hipStream_t pst) {
+    std::vector<size_t> need;
+    const std::vector<QueryCounts> counts = measure_counts(idx, ws, pb, pst, need);
     for (size_t k = 0; k < need.size(); ++k) {
         CompiledQuery& q = pb.queries[need[k]];
         q = compile_query(idx, *reqs[need[k]], tables.later_pass(&counts[k]));
@@ -491,10 +498,10 @@ static void compile_with_counts(const Index& idx, Workspace& ws, PartialBatch& p
     }
 }
 
-// Dictionary scans (fuzzy / prefix leaves) of the whole batch, then its compilation passes with the pre-passes between them: pb.queries
-static CompileReport compile_batch(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, hipStream_t st) {
-    CompileReport rep;
-    BatchTables tables;
+// Dictionary scans (fuzzy / prefix leaves) of the whole batch, then its compilation passes up to the count pre-pass, with the job pre-passes
+// between them: pb.queries, where a query that IS a count pre-pass still waits for its numbers.  Returns the pre-passes' stream.
+static hipStream_t compile_before_counts(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, hipStream_t st, BatchTables& tables,
+                                         CompileReport& rep) {
     for (size_t i = 0; i < n; ++i)
         if (reqs[i]) collect_fuzzy_probes(idx, *reqs[i], tables.fuzzy);
     static const bool pre_own = std::getenv("VQ_PRE_ON_SCAN_STREAM") == nullptr;
@@ -513,6 +520,14 @@ static CompileReport compile_batch(const Index& idx, Workspace& ws, PartialBatch
         std::fprintf(stderr, "\n");
     }
     compile_with_jobs(idx, ws, pb, reqs, order, heavy_first, tables, pst, rep);
+    return pst;
+}
+
+// The whole compilation of a batch: the passes above, the count pre-pass and the final compilation of the queries that asked for it
+static CompileReport compile_batch(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, hipStream_t st) {
+    CompileReport rep;
+    BatchTables tables;
+    const hipStream_t pst = compile_before_counts(idx, ws, pb, reqs, n, st, tables, rep);
     compile_with_counts(idx, ws, pb, reqs, tables, pst);
     rep.t_compiled = now_ms();
     rep.probes = tables.fuzzy.size(), rep.unions = tables.unions.size(), rep.ranges = tables.ranges.size();
@@ -892,6 +907,37 @@ void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStr
         std::lock_guard<std::mutex> g(idx.profile_mutex);
         account_timed_launches(idx.profile, ws);
     }
+}
+
+// vq_debug_node_counts (capi.cpp): a batch's compilation up to and including its count pre-pass — the dictionary scans and job pre-passes its
+// leaves need first, run_count_queries on the queries that are one —, and no result scan
+std::vector<NodeCounts> debug_node_counts(const Index& idx, const vqreq::Request* const* reqs, size_t n, bool summed) {
+    std::vector<NodeCounts> out(n);
+    debug_prepass(idx, [&](Workspace& ws, hipStream_t) {
+        PartialBatch pb;
+        pb.index = &idx;
+        BatchTables tables;
+        CompileReport rep;
+        const hipStream_t pst = compile_before_counts(idx, ws, pb, reqs, n, idx.stream, tables, rep);
+        for (size_t i = 0; i < n; ++i) {
+            const CompiledQuery& q = pb.queries[i];
+            out[i].status = q.status == kStatusNeedsCounts ? 0 : q.status == 0 ? kNodeCountsNone : q.status > 0 ? q.status : int(ERR_UNSUPPORTED);
+            if (q.status != 0 && q.status != kStatusNeedsCounts) out[i].error = q.error;
+            if (q.status == kStatusNeedsCounts) out[i].n_spans = q.n_spans, out[i].tile_words = q.tile_words;
+        }
+        std::vector<size_t> need;
+        const std::vector<QueryCounts> counts = measure_counts(idx, ws, pb, pst, need, summed);
+        for (size_t k = 0; k < need.size(); ++k) {
+            NodeCounts& o = out[need[k]];
+            o.has_filter = counts[k].has_filter;
+            o.filter_count = counts[k].filter_count;
+            for (uint32_t node : pb.queries[need[k]].count_nodes) {  // in counter order
+                const auto& c = counts[k].nodes.at(node);
+                o.nodes.push_back({node, c.first, c.second});
+            }
+        }
+    });
+    return out;
 }
 
 // The dictionary scans of a suggest / highlight request, answered: on the next workspace in turn, on the pre-passes' stream

@@ -390,6 +390,34 @@ def search_batch(requests, index, raise_on_error=True, docsets=None):
     return results
 
 
+COUNTS_NONE = -1  # VQ_COUNTS_NONE: the request needs no count pre-pass
+
+
+def debug_node_counts(requests, index, summed=True, docsets=None):
+    """`vq_debug_node_counts`: what the count pre-pass measures for the requests as one batch, no result scan.  -> one dict per request:
+    status (0 counted, COUNTS_NONE, or the error code its search would return), has_filter, filter_count, n_spans, tile_words and
+    nodes = [(node id, hits, hits inside the filter)] in counter order.  `summed`: after the sum over the shards (else this shard's numbers)."""
+    L = _lib.lib()
+    reqs = _with_docsets(requests, docsets)
+    n = len(reqs)
+    arr = (C.c_void_p * n)(*[r.h for r in reqs])
+    cap = 256 * max(n, 1)  # (a count query has at most 127 measured nodes)
+    status = np.zeros(n, np.int32)
+    has_filter, n_spans, tile_words, node_ids = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(cap, np.uint32)
+    filter_count, node_off, hits, inside = np.zeros(n, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = L.vq_debug_node_counts(index.h, arr, n, int(bool(summed)), cap, p(status), p(has_filter), p(filter_count), p(n_spans), p(tile_words), p(node_off),
+                                p(node_ids), p(hits), p(inside))
+    if rc != 0:
+        raise VelociError(5 if rc == -1 else 6, "vq_debug_node_counts: %d (%s)" % (rc, L.vq_last_error().decode("utf-8", "replace")))
+    out = []
+    for i in range(n):
+        lo, hi = int(node_off[i]), int(node_off[i + 1])
+        out.append({"status": int(status[i]), "has_filter": bool(has_filter[i]), "filter_count": int(filter_count[i]), "n_spans": int(n_spans[i]),
+                    "tile_words": int(tile_words[i]), "nodes": [(int(node_ids[k]), int(hits[k]), int(inside[k])) for k in range(lo, hi)]})
+    return out
+
+
 class RequestBatch:
     """n parsed requests as one C array: build once, search many times (the throughput path)."""
 

@@ -183,14 +183,22 @@ typedef struct vq_docset vq_docset;
 /* ids: n u32 anchor ids, any order, duplicates allowed; ids_on_device != 0: `ids` is device memory on the index's GPU (4-byte aligned, complete before
  * the call).  VQ_ERR_INVALID_ARGUMENT when an id is >= the index's number of anchors (the count is in vq_last_error).  Synchronous. */
 int vq_docset_create(const vq_index*, const uint32_t* ids, uint64_t n, int ids_on_device, vq_docset** out);
+/* The set a filter tree selects, evaluated once on the device.  filter_json: a SearchRequest tree, exactly what Request.filter holds (a leaf, or
+ * and / or over trees).  within: NULL, or a set of the same index that is and-ed in.  The ids are exactly those the filter of a request with `filter`
+ * = this tree and doc set = `within` selects, so a search with the resulting set attached answers bit for bit what the same search answers with the
+ * tree as its `filter`.  Every decline and error is the one that search returns (unknown path, more than 64 lists, a filter that reduces to
+ * nothing, ...); VQ_ERR_JSON for text that does not parse, VQ_ERR_INVALID_ARGUMENT for a `within` of another index.  On a shard the set's length is
+ * the sum over the shards: one u64 goes through the hook of vq_index_set_allreduce (every rank calls in the same order); without the hook a shard
+ * answers VQ_ERR_UNSUPPORTED.  The result is an ordinary doc set, also as the `within` of another call.  Synchronous. */
+int vq_docset_from_filter(const vq_index*, const char* filter_json, size_t len, const vq_docset* within, vq_docset** out);
 uint64_t vq_docset_len(const vq_docset*);        /* unique ids of the whole set (the same on every shard) */
 uint64_t vq_docset_local_len(const vq_docset*);  /* those inside this index's doc range */
 uint64_t vq_docset_device_bytes(const vq_docset*);
 /* self-check (tests): part 0 = the local ids without padding, 1 = bitmap words, 2 = rank_dir, 3 = tile_dir, 4 = the local ids with their padding to
  * a multiple of 4 entries; returns the element count (0: the set carries no such part), copies min(count, cap) elements */
 uint64_t vq_debug_docset_part(const vq_docset*, int part, uint32_t* out, uint64_t cap);
-/* measurement: with VQ_DOCSET_TIMING=1 in the environment a set records the HIP event times (ms) of its construction — marking the ids, counting and
- * scanning, expanding; 0, or -1 when the set recorded none */
+/* measurement: with VQ_DOCSET_TIMING=1 in the environment a set records the HIP event times (ms) of its construction — marking the ids (a set from a filter: evaluating
+ * the filter's program), counting and scanning, expanding; 0, or -1 when the set recorded none */
 int vq_debug_docset_timings(const vq_docset*, float* ms_mark, float* ms_count_scan, float* ms_expand);
 void vq_docset_free(vq_docset*);
 /* attaches the set to the request (NULL detaches).  The request keeps the set alive: freeing the handle afterwards is allowed. */

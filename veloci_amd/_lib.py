@@ -24,7 +24,7 @@ SYMBOLS = [
     "vq_comm_unique_id", "vq_comm_init", "vq_comm_init_custom", "vq_comm_destroy", "vq_shard_step_begin", "vq_shard_step_end", "vq_shard_step_free", "vq_shard_step_flat",
     "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_debug_union_lists", "vq_debug_locality_lists",
     "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_version",
-    "vq_docset_create", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
+    "vq_docset_create", "vq_docset_from_filter", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
     "vq_request_set_docset",
 ]
 COMM_ID_BYTES = 128
@@ -156,6 +156,7 @@ def lib():
         "vq_profile_read": (i, [vp, i, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64)]),
         "vq_profile_enable": (i, [vp, i]),
         "vq_docset_create": (i, [vp, vp, u64, i, C.POINTER(vp)]),
+        "vq_docset_from_filter": (i, [vp, C.c_char_p, C.c_size_t, vp, C.POINTER(vp)]),
         "vq_docset_len": (u64, [vp]),
         "vq_docset_local_len": (u64, [vp]),
         "vq_docset_device_bytes": (u64, [vp]),

@@ -769,6 +769,22 @@ int vq_docset_create(const vq_index* index, const uint32_t* ids, uint64_t n, int
         *out = h;
     });
 }
+int vq_docset_from_filter(const vq_index* index, const char* filter_json, size_t len, const vq_docset* within, vq_docset** out) {
+    return guard([&] {
+        if (!index || !filter_json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_from_filter: null argument");
+        *out = nullptr;
+        std::optional<vqreq::SearchRequest> filter;
+        try {
+            filter = vqreq::search_request_from_json(vqjson::parse(filter_json, len));
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        auto set = vq::make_docset_from_filter(*index->idx, *filter, within ? within->set : nullptr);
+        auto* h = new vq_docset();
+        h->set = std::move(set);
+        *out = h;
+    });
+}
 uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
 uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }
 uint64_t vq_docset_device_bytes(const vq_docset* d) { return d ? d->set->device_bytes : 0; }

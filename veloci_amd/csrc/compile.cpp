@@ -1930,6 +1930,19 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         cq.simple_n = 0;
     }
 
+    // ------------------------------------------------------------ a filter and nothing else (Request::filter_only)
+    // What run() does for `filter` and `docset`, in its order, and none of the rest: cq.fops over cq.lists, the stack depth the program reaches.
+    void run_filter_only() {
+        if (!req.filter) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"filter is None, but is required for a doc set from a filter\" ");
+        collect(*req.filter, true);
+        flag_tree(*req.filter);
+        uint32_t sp = 0;
+        compile_node(*req.filter, true, cq.fops, sp, {});
+        if (cq.fops.empty()) unsupported("filter that reduces to nothing");
+        if (req.docset) emit_docset_leaf(sp);
+        cq.stack_depth = std::max<uint32_t>(max_depth, 1);
+    }
+
     // ------------------------------------------------------------ the whole request (search.rs:143-228)
     void run() {
         cq.lists.reserve(8);  // (the vectors of a typical request: one allocation each instead of a growth chain)
@@ -1937,6 +1950,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         cq.pres.reserve(8);
         cq.pres_in.reserve(16);
         by_address.reserve(8);
+        if (req.filter_only) return run_filter_only();
         // (`select` itself is not looked at: search::search leaves the reading of the selected fields to to_documents, search.rs:63-103; together with
         //  why_found it asks for why_found_info, :220-224 — complete_why_found_requests)
         // (`suggest` is not looked at either: search::search reads search_req, search.rs:151-155; suggest_multi is vq_suggest_json)

@@ -1,15 +1,16 @@
 // Host side of the doc sets (DocSet, engine.hpp): buffers, the launch sequence of docset.hip, the rules of index.cpp for which parts a list carries.
 #include <cstdlib>
+#include <functional>
 
 #include "engine.hpp"
 
 namespace vq {
 
-std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids, uint64_t n, bool on_device) {
-    if (n && !ids) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "doc set: null ids");
-    if (on_device && (reinterpret_cast<uintptr_t>(ids) & 3u)) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "doc set: device ids are not 4-byte aligned");
-    VQ_HIP(hipSetDevice(idx.device));
-    const hipStream_t st = idx.pre_stream ? idx.pre_stream : idx.stream;
+// The image from a filled scratch bitmap: `mark` queues on `st` whatever sets bit `doc` of the zeroed scratch bitmap over all anchors (and may count
+// into meta[0] what it refused); count -> scan -> expand -> tiles follow.  len is the popcount of the whole scratch bitmap.  n: the ids of the
+// caller's array, for the message about the refused ones
+using MarkFn = std::function<void(hipStream_t st, uint32_t* scratch, uint64_t scratch_words, unsigned long long* meta)>;
+static std::shared_ptr<DocSet> docset_from_marks(const Index& idx, hipStream_t st, uint64_t n, const MarkFn& mark) {
     static const bool timing = std::getenv("VQ_DOCSET_TIMING") != nullptr;
 
     auto ds = std::make_shared<DocSet>();
@@ -22,7 +23,7 @@ std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids,
     const uint64_t scratch_words = ((uint64_t(idx.num_anchors) + 511u) / 512u) * 16u;  // the whole anchor range, in whole 512-doc blocks
     const uint64_t base_word = idx.bitmap_base >> 5;
 
-    DevBuf d_ids, scratch, local, rank, partials, meta;
+    DevBuf scratch, local, rank, partials, meta;
     scratch.alloc(scratch_words * 4 + 16);
     local.alloc(words * 4 + 16);
     rank.alloc((blocks + 1) * 4 + 16);
@@ -30,11 +31,6 @@ std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids,
     meta.alloc(16);
     VQ_HIP(hipMemsetAsync(scratch.p, 0, scratch.bytes, st));
     VQ_HIP(hipMemsetAsync(meta.p, 0, meta.bytes, st));
-    if (n && !on_device) {
-        d_ids.alloc(n * 4 + 16);
-        d_ids.upload(ids, n * 4, st);
-        ids = d_ids.as<uint32_t>();
-    }
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     struct EventGuard {
         hipEvent_t* ev;
@@ -49,7 +45,7 @@ std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids,
         if (timing) VQ_HIP(hipEventRecord(ev[i], st));
     };
     stamp(0);
-    launch_docset_mark(st, ids, n, idx.num_anchors, scratch.as<uint32_t>(), meta.as<unsigned long long>());
+    mark(st, scratch.as<uint32_t>(), scratch_words, meta.as<unsigned long long>());
     stamp(1);
     launch_docset_count(st, scratch.as<uint32_t>(), scratch_words, base_word, words, idx.bitmap_base, idx.doc_lo, idx.doc_hi, local.as<uint32_t>(), rank.as<uint32_t>(),
                         meta.as<unsigned long long>());
@@ -91,6 +87,35 @@ std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids,
         ds->rank_dir = std::move(rank);
     }
     ds->device_bytes = ds->docs.bytes + ds->bitmap.bytes + ds->rank_dir.bytes + ds->tile_dir.bytes;
+    return ds;
+}
+
+std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids, uint64_t n, bool on_device) {
+    if (n && !ids) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "doc set: null ids");
+    if (on_device && (reinterpret_cast<uintptr_t>(ids) & 3u)) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "doc set: device ids are not 4-byte aligned");
+    VQ_HIP(hipSetDevice(idx.device));
+    const hipStream_t st = idx.pre_stream ? idx.pre_stream : idx.stream;
+    DevBuf d_ids;
+    if (n && !on_device) {
+        d_ids.alloc(n * 4 + 16);
+        d_ids.upload(ids, n * 4, st);
+        ids = d_ids.as<uint32_t>();
+    }
+    return docset_from_marks(idx, st, n, [&](hipStream_t s, uint32_t* scratch, uint64_t, unsigned long long* meta) { launch_docset_mark(s, ids, n, idx.num_anchors, scratch, meta); });
+}
+
+// The set a compiled filter selects (exec.cpp: make_docset_from_filter compiled it and staged `lists` and `fops` on the device).  `st` is the stream
+// the compilation's pre-passes ran on.  The scratch bitmap holds the shard's docs only, so its popcount is local: len is the sum over the shards
+std::shared_ptr<const DocSet> make_docset_from_program(const Index& idx, hipStream_t st, const DList* lists, uint32_t n_lists, const DOp* fops, uint32_t n_fops,
+                                                       uint32_t stack_depth) {
+    auto ds = docset_from_marks(idx, st, 0, [&](hipStream_t s, uint32_t* scratch, uint64_t scratch_words, unsigned long long*) {
+        launch_docset_filter(s, lists, n_lists, fops, n_fops, stack_depth, idx.doc_lo, idx.doc_hi, scratch, scratch_words);
+    });
+    if (idx.sharded()) {
+        std::vector<uint64_t> total{ds->len};
+        idx.sum_over_shards(total);
+        ds->len = total[0];
+    }
     return ds;
 }
 

@@ -644,6 +644,10 @@ struct DocSet {
 // ids: n anchor ids in any order, duplicates allowed, in host memory or (on_device) in the index's GPU's memory.  Synchronous.  An id >= num_anchors:
 // ERR_INVALID_ARGUMENT, with their number in the message
 std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids, uint64_t n, bool on_device);
+// The set of the docs a compiled filter selects: the presence-only postfix program fops over lists, both staged on the device (docset_filter.hip fills
+// the scratch bitmap, the rest is make_docset's).  Synchronous, on `st`.  On a shard len is summed over the shards (Index::sum_over_shards)
+std::shared_ptr<const DocSet> make_docset_from_program(const Index& idx, hipStream_t st, const DList* lists, uint32_t n_lists, const DOp* fops, uint32_t n_fops,
+                                                       uint32_t stack_depth);
 
 // ------------------------------------------------------------------ compiled query
 struct HList {
@@ -781,6 +785,10 @@ void run_range_jobs(const Index& idx, Workspace& ws, RangeTable& table, const Un
 // (VQ_UNION_DENSE_MIN, else 64 x 64)
 void run_union_jobs(const Index& idx, Workspace& ws, UnionTable& table, hipStream_t st, int64_t dense_min = -1);
 void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStream_t)>& body);  // exec.cpp: what vq_debug_*_lists run the drivers in
+// vq_docset_from_filter (exec.cpp): the ids the compiler's filter of a request with `filter` and doc set `within` (null: none) selects, as a doc set.
+// The tree is compiled as a filter and nothing else (Request::filter_only) behind the dictionary scans and job pre-passes a batch gives it; every
+// decline and error is the one a search with this filter returns
+std::shared_ptr<const DocSet> make_docset_from_filter(const Index& idx, const vqreq::SearchRequest& filter, std::shared_ptr<const DocSet> within);
 // What the count pre-pass measured for one request of a batch (vq_debug_node_counts).  status: 0 = counted, kNodeCountsNone = the request needs no
 // count pre-pass, otherwise the error code its search would return (`error`: the text)
 constexpr int kNodeCountsNone = -1;

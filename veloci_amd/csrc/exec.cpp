@@ -909,16 +909,22 @@ void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStr
     }
 }
 
+// A batch's compilation up to the count pre-pass and nothing launched behind it, on a workspace debug_prepass took: where vq_debug_node_counts and
+// vq_docset_from_filter start.  Returns the pre-passes' stream.
+static hipStream_t compile_without_scan(const Index& idx, Workspace& ws, PartialBatch& pb, const vqreq::Request* const* reqs, size_t n, BatchTables& tables) {
+    pb.index = &idx;
+    CompileReport rep;
+    return compile_before_counts(idx, ws, pb, reqs, n, idx.stream, tables, rep);
+}
+
 // vq_debug_node_counts (capi.cpp): a batch's compilation up to and including its count pre-pass — the dictionary scans and job pre-passes its
 // leaves need first, run_count_queries on the queries that are one —, and no result scan
 std::vector<NodeCounts> debug_node_counts(const Index& idx, const vqreq::Request* const* reqs, size_t n, bool summed) {
     std::vector<NodeCounts> out(n);
     debug_prepass(idx, [&](Workspace& ws, hipStream_t) {
         PartialBatch pb;
-        pb.index = &idx;
         BatchTables tables;
-        CompileReport rep;
-        const hipStream_t pst = compile_before_counts(idx, ws, pb, reqs, n, idx.stream, tables, rep);
+        const hipStream_t pst = compile_without_scan(idx, ws, pb, reqs, n, tables);
         for (size_t i = 0; i < n; ++i) {
             const CompiledQuery& q = pb.queries[i];
             out[i].status = q.status == kStatusNeedsCounts ? 0 : q.status == 0 ? kNodeCountsNone : q.status > 0 ? q.status : int(ERR_UNSUPPORTED);
@@ -936,6 +942,51 @@ std::vector<NodeCounts> debug_node_counts(const Index& idx, const vqreq::Request
                 o.nodes.push_back({node, c.first, c.second});
             }
         }
+    });
+    return out;
+}
+
+// vq_docset_from_filter (capi.cpp): the filter compiled alone, as a batch of one compiles it up to the count pre-pass (a filter has no score sums
+// to order: there is none) — dictionary scans first, the job pre-passes a leaf asks for —, its lists and program staged in one blob (pack_blob: the
+// inline lists travel inside it), then the doc set's image from the program's bits.  The workspace is held until the image is built: a job's
+// result lives in it.
+std::shared_ptr<const DocSet> make_docset_from_filter(const Index& idx, const vqreq::SearchRequest& filter, std::shared_ptr<const DocSet> within) {
+    if (within && within->index_uid != idx.uid) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "the doc set to search within was made for another index");
+    if (!idx.can_sum_over_shards())  // the set's length is a sum over the shards
+        throw VelociError(ERR_UNSUPPORTED, "unsupported on the MI355X query path: doc set from a filter on a sharded index without vq_index_set_allreduce");
+    vqreq::Request req;
+    req.filter = filter;
+    req.docset = std::move(within);
+    req.filter_only = true;
+    std::shared_ptr<const DocSet> out;
+    debug_prepass(idx, [&](Workspace& ws, hipStream_t) {
+        PartialBatch pb;
+        BatchTables tables;
+        const vqreq::Request* reqs[1] = {&req};
+        const hipStream_t pst = compile_without_scan(idx, ws, pb, reqs, 1, tables);
+        const CompiledQuery& cq = pb.queries[0];
+        if (cq.status > 0) throw VelociError(cq.status, cq.error);
+        if (cq.status < 0) throw VelociError(ERR_UNSUPPORTED, "unsupported on the MI355X query path: filter still needs a pre-pass after its jobs ran (internal)");
+        // what the kernel relies on: the stack never holds more than stack_depth entries and ends with one, every list exists
+        uint32_t sp = 0;
+        for (const DOp& op : cq.fops) {
+            bool ok = true;
+            if (op.kind == OP_LEAF) ok = size_t(op.list_begin) + op.list_count <= cq.lists.size();
+            else if ((op.kind == OP_AND || op.kind == OP_OR) && op.nchild >= 1 && op.nchild <= sp) sp -= op.nchild;
+            else ok = false;
+            if (!ok || ++sp > cq.stack_depth) throw VelociError(ERR_UNSUPPORTED, "unsupported on the MI355X query path: malformed filter program (internal)");
+        }
+        if (sp != 1 || cq.stack_depth > uint32_t(kStackDepth)) throw VelociError(ERR_UNSUPPORTED, "unsupported on the MI355X query path: malformed filter program (internal)");
+        const size_t bytes = pack_blob(cq, idx, nullptr, nullptr, 0, 0, {}, {});
+        std::vector<uint8_t> host(bytes);
+        DevBuf blob;
+        blob.alloc(bytes + 16);
+        pack_blob(cq, idx, host.data(), blob.as<uint8_t>(), 0, 0, {}, {});
+        blob.upload(host.data(), bytes, pst);
+        QHeader h;
+        std::memcpy(&h, host.data(), sizeof h);
+        out = make_docset_from_program(idx, pst, reinterpret_cast<const DList*>(blob.as<uint8_t>() + h.off_lists), h.n_lists,
+                                       reinterpret_cast<const DOp*>(blob.as<uint8_t>() + h.off_fops), h.n_fops, cq.stack_depth);
     });
     return out;
 }

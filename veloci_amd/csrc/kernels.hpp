@@ -180,6 +180,12 @@ void launch_docset_scan(hipStream_t st, uint32_t* rank_dir, uint64_t blocks, uin
 void launch_docset_tiles(hipStream_t st, const uint32_t* rank_dir, uint64_t blocks, uint32_t* tile_dir, uint64_t entries);
 // docs[rank] = every set bit of the local bitmap as a doc id, ascending, then 0xFFFFFFFF up to a multiple of 4 entries
 void launch_docset_expand(hipStream_t st, const uint32_t* local, const uint32_t* rank_dir, uint64_t words, uint32_t bitmap_base, uint32_t* docs);
+// ---- doc sets from a filter (docset_filter.hip): bit `doc` of the zeroed scratch bitmap is set for every doc the presence-only postfix program
+// fops[0 .. n_fops) over lists[0 .. n_lists) selects (both in device memory; OP_LEAF = the union of its lists, OP_AND / OP_OR over nchild stack
+// entries).  The program never holds more than stack_depth <= kStackDepth entries and leaves one; every list index lies below n_lists; the lists
+// hold docs of [doc_lo, doc_hi) only, their bitmaps and directories start at doc_lo rounded down to 65536.  scratch_words: a multiple of 16
+void launch_docset_filter(hipStream_t st, const DList* lists, uint32_t n_lists, const DOp* fops, uint32_t n_fops, uint32_t stack_depth, uint32_t doc_lo, uint32_t doc_hi,
+                          uint32_t* scratch, uint64_t scratch_words);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

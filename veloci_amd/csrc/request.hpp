@@ -108,6 +108,9 @@ struct Request {  // src/search/request/mod.rs:15-87
     // never parsed, never printed: the doc set attached to the request (vq_request_set_docset).  The request behaves as if its filter were one more
     // leaf whose hits_ids are the set's ids (and-ed with `filter` when there is one); the request keeps the set alive
     std::shared_ptr<const vq::DocSet> docset;
+    // never parsed, never printed: compile `filter` (and `docset`) as a filter and nothing else — no score tree, no sinks, no count pre-pass; the
+    // compiled query holds fops over lists only (vq_docset_from_filter)
+    bool filter_only = false;
     bool filtered() const { return filter.has_value() || docset != nullptr; }  // "has a filter", wherever the reference asks that of a request
     bool exact_routes_only = false;  // (internal) second run of a request whose speculative route could not be confirmed: no k_scan_probe_or
 };

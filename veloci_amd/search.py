@@ -77,6 +77,24 @@ class DocSet:
         self.h = h
         del keep
 
+    @classmethod
+    def from_filter(cls, index, filter, within=None):
+        """The set of the docs a filter tree selects (`vq_docset_from_filter`), evaluated once on the index's GPU.  `filter`: what `Request.filter`
+        holds, as a dict or JSON text (str / bytes); `within`: a DocSet of the same index that is and-ed in.  The ids are exactly those the filter of a
+        request with this `filter` and doc set `within` selects, so `search(r, index, docset=DocSet.from_filter(index, f))` answers what `search`
+        answers for `r` with `filter: f`.  On a shard the length is summed over the shards through `index.set_allreduce`'s hook."""
+        if isinstance(filter, dict):
+            filter = json.dumps(filter)
+        if isinstance(filter, str):
+            filter = filter.encode()
+        self = cls.__new__(cls)
+        self.L = _lib.lib()
+        self.h = None
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_from_filter(index.h, filter, len(filter), within._handle() if within is not None else None, C.byref(h)))
+        self.h = h
+        return self
+
     def _handle(self):
         if not self.h:
             raise ValueError("DocSet: used after close()")

@@ -191,6 +191,24 @@ int vq_docset_create(const vq_index*, const uint32_t* ids, uint64_t n, int ids_o
  * the sum over the shards: one u64 goes through the hook of vq_index_set_allreduce (every rank calls in the same order); without the hook a shard
  * answers VQ_ERR_UNSUPPORTED.  The result is an ordinary doc set, also as the `within` of another call.  Synchronous. */
 int vq_docset_from_filter(const vq_index*, const char* filter_json, size_t len, const vq_docset* within, vq_docset** out);
+/* Set algebra over staged sets of one index, on the device.  AND / OR: n >= 1 operands (n == 1: a set equal to the operand).  MINUS: n >= 1,
+ * sets[0] without the ids of any of sets[1 .. n).  NOT: n == 1, every anchor of the index's doc range that is not in the set (never an id >= the
+ * number of anchors).  n has no upper bound.  The result is an ordinary, immutable doc set: attached to a request, as `within`, as an operand of
+ * another combine.  Synchronous; any number of threads may call concurrently, also on shared operands, which are only read and may be freed right
+ * after the call.  Two routes fill the result's bitmap: the word route folds the operands' bitmap words; the probe route — an AND with at least one
+ * operand that carries no bitmap, a MINUS whose minuend carries none — streams the smallest such operand's ids and tests each against the others,
+ * so its cost follows the small set.  VQ_NO_SETOP_PROBE=1 in the environment (read at every call) sends everything through the word route.
+ * VQ_ERR_INVALID_ARGUMENT for n == 0, a null operand, an unknown op, NOT with n != 1, an operand made for another index.  On a shard the
+ * result's length is the sum over the shards: one u64 goes through the hook of vq_index_set_allreduce (every rank calls in the same order); without
+ * the hook a shard answers VQ_ERR_UNSUPPORTED.  An unsharded index never calls the hook. */
+enum { VQ_DOCSET_AND = 0, VQ_DOCSET_OR = 1, VQ_DOCSET_MINUS = 2, VQ_DOCSET_NOT = 3 };
+int vq_docset_combine(const vq_index*, int op, const vq_docset* const* sets, size_t n, vq_docset** out);
+/* The set's ids inside this index's doc range — sorted, unique, unpadded — to `out`: host memory, or with out_on_device != 0 device memory on the
+ * index's GPU (4-byte aligned; copied device to device on the library's stream, finished when the call returns; the index must still exist).  At
+ * most `cap` ids are copied; returns the local length (0 with the reason in vq_last_error when the copy failed). */
+uint64_t vq_docset_ids(const vq_docset*, uint32_t* out, uint64_t cap, int out_on_device);
+/* self-check (tests): -1 for a set no combine made, 0 when the word route built it, 1 when the probe route did */
+int vq_debug_docset_route(const vq_docset*);
 uint64_t vq_docset_len(const vq_docset*);        /* unique ids of the whole set (the same on every shard) */
 uint64_t vq_docset_local_len(const vq_docset*);  /* those inside this index's doc range */
 uint64_t vq_docset_device_bytes(const vq_docset*);

@@ -785,6 +785,29 @@ int vq_docset_from_filter(const vq_index* index, const char* filter_json, size_t
         *out = h;
     });
 }
+int vq_docset_combine(const vq_index* index, int op, const vq_docset* const* sets, size_t n, vq_docset** out) {
+    return guard([&] {
+        if (!index || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_combine: null argument");
+        *out = nullptr;
+        if (!n || !sets) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_combine: no operands");
+        std::vector<std::shared_ptr<const DocSet>> operands(n);  // held for the length of the call
+        for (size_t i = 0; i < n; ++i) {
+            if (!sets[i]) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_combine: operand " + std::to_string(i) + " is null");
+            operands[i] = sets[i]->set;
+        }
+        auto set = vq::combine_docsets(*index->idx, op, operands);
+        auto* h = new vq_docset();
+        h->set = std::move(set);
+        *out = h;
+    });
+}
+uint64_t vq_docset_ids(const vq_docset* d, uint32_t* out, uint64_t cap, int out_on_device) {
+    if (!d) return 0;
+    uint64_t n = 0;
+    if (guard([&] { n = vq::copy_docset_ids(*d->set, out, cap, out_on_device != 0); }) != VQ_OK) return 0;  // (the reason is in vq_last_error)
+    return n;
+}
+int vq_debug_docset_route(const vq_docset* d) { return d ? d->set->route : -1; }
 uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
 uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }
 uint64_t vq_docset_device_bytes(const vq_docset* d) { return d ? d->set->device_bytes : 0; }

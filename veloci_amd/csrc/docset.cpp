@@ -6,11 +6,8 @@
 
 namespace vq {
 
-// The image from a filled scratch bitmap: `mark` queues on `st` whatever sets bit `doc` of the zeroed scratch bitmap over all anchors (and may count
-// into meta[0] what it refused); count -> scan -> expand -> tiles follow.  len is the popcount of the whole scratch bitmap.  n: the ids of the
-// caller's array, for the message about the refused ones
-using MarkFn = std::function<void(hipStream_t st, uint32_t* scratch, uint64_t scratch_words, unsigned long long* meta)>;
-static std::shared_ptr<DocSet> docset_from_marks(const Index& idx, hipStream_t st, uint64_t n, const MarkFn& mark) {
+// The image from a filled scratch bitmap (engine.hpp)
+std::shared_ptr<DocSet> docset_from_marks(const Index& idx, hipStream_t st, uint64_t n, const DocSetMarkFn& mark) {
     static const bool timing = std::getenv("VQ_DOCSET_TIMING") != nullptr;
 
     auto ds = std::make_shared<DocSet>();
@@ -18,9 +15,11 @@ static std::shared_ptr<DocSet> docset_from_marks(const Index& idx, hipStream_t s
     ds->num_anchors = idx.num_anchors;
     ds->doc_lo = idx.doc_lo;
     ds->doc_hi = idx.doc_hi;
+    ds->device = idx.device;
+    ds->stream = st;
     // the image of index.cpp: `words` words from bitmap_base on, one rank entry per 512 docs plus the closing one
     const uint64_t words = idx.bitmap_words, blocks = words >> (kRankShift - 5);
-    const uint64_t scratch_words = ((uint64_t(idx.num_anchors) + 511u) / 512u) * 16u;  // the whole anchor range, in whole 512-doc blocks
+    const uint64_t scratch_words = docset_scratch_words(idx);
     const uint64_t base_word = idx.bitmap_base >> 5;
 
     DevBuf scratch, local, rank, partials, meta;

@@ -640,7 +640,16 @@ struct DocSet {
     DevBuf docs, bitmap, rank_dir, tile_dir;
     uint64_t device_bytes = 0;
     float ms_mark = -1.0f, ms_count_scan = -1.0f, ms_expand = -1.0f;  // VQ_DOCSET_TIMING=1: HIP event times of the three stages of its construction
+    int route = -1;                // combine_docsets: 0 the word route built it, 1 the probe route; -1: no combine made it
+    int device = 0;                // the index's GPU and the stream the set was built on (its index's: vq_docset_ids copies on it)
+    hipStream_t stream = nullptr;
 };
+// The image from a filled scratch bitmap: `mark` queues on `st` whatever sets bit `doc` of the zeroed scratch bitmap over all anchors (and may count
+// into meta[0] what it refused); count -> scan -> expand -> tiles follow.  len is the popcount of the whole scratch bitmap.  n: the ids of the
+// caller's array, for the message about the refused ones
+using DocSetMarkFn = std::function<void(hipStream_t st, uint32_t* scratch, uint64_t scratch_words, unsigned long long* meta)>;
+std::shared_ptr<DocSet> docset_from_marks(const Index& idx, hipStream_t st, uint64_t n, const DocSetMarkFn& mark);
+inline uint64_t docset_scratch_words(const Index& idx) { return ((uint64_t(idx.num_anchors) + 511u) / 512u) * 16u; }  // the whole anchor range, in whole 512-doc blocks
 // ids: n anchor ids in any order, duplicates allowed, in host memory or (on_device) in the index's GPU's memory.  Synchronous.  An id >= num_anchors:
 // ERR_INVALID_ARGUMENT, with their number in the message
 std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids, uint64_t n, bool on_device);
@@ -648,6 +657,14 @@ std::shared_ptr<const DocSet> make_docset(const Index& idx, const uint32_t* ids,
 // the scratch bitmap, the rest is make_docset's).  Synchronous, on `st`.  On a shard len is summed over the shards (Index::sum_over_shards)
 std::shared_ptr<const DocSet> make_docset_from_program(const Index& idx, hipStream_t st, const DList* lists, uint32_t n_lists, const DOp* fops, uint32_t n_fops,
                                                        uint32_t stack_depth);
+// Set algebra over staged sets of `idx` (docset_algebra.cpp, docset_algebra.hip): op 0 and, 1 or, 2 minus (sets[0] without the others), 3 not
+// (n == 1: the anchors of [doc_lo, doc_hi) outside the set).  Any n >= 1.  Synchronous; each call owns its scratch, operands are only read.
+// On a shard len is summed over the shards (Index::sum_over_shards)
+enum { SETOP_AND = 0, SETOP_OR = 1, SETOP_MINUS = 2, SETOP_NOT = 3 };
+std::shared_ptr<const DocSet> combine_docsets(const Index& idx, int op, const std::vector<std::shared_ptr<const DocSet>>& sets);
+// The set's local ids (sorted, unique, unpadded): min(local_len, cap) of them to `out`, host memory or (on_device) memory of the set's GPU — then
+// device to device on the set's stream, finished on return.  Returns local_len
+uint64_t copy_docset_ids(const DocSet& ds, uint32_t* out, uint64_t cap, bool on_device);
 
 // ------------------------------------------------------------------ compiled query
 struct HList {

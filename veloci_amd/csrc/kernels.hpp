@@ -186,6 +186,28 @@ void launch_docset_expand(hipStream_t st, const uint32_t* local, const uint32_t*
 // hold docs of [doc_lo, doc_hi) only, their bitmaps and directories start at doc_lo rounded down to 65536.  scratch_words: a multiple of 16
 void launch_docset_filter(hipStream_t st, const DList* lists, uint32_t n_lists, const DOp* fops, uint32_t n_fops, uint32_t stack_depth, uint32_t doc_lo, uint32_t doc_hi,
                           uint32_t* scratch, uint64_t scratch_words);
+// ---- doc set algebra (docset_algebra.hip): the scratch bitmap filled from staged sets.  An operand: its bitmap image (null: the set carries none;
+// `words` words from the index's bitmap base on) and its sorted local ids (16-byte aligned, padded to a multiple of 4 entries, all inside
+// [doc_lo, doc_hi)).  A launch takes up to kSetOpTable operands; the caller runs longer lists in rounds
+struct SetOperand {
+    const uint32_t* bitmap;
+    const uint32_t* docs;
+    uint32_t len, pad;
+};
+constexpr uint32_t kSetOpTable = 8;
+struct SetOpTable {
+    SetOperand o[kSetOpTable];
+};
+// local word j (scratch word base_word + j, as far as the scratch bitmap reaches) = is_or ? old | o[0] | .. | o[n - 1]
+//   : (init_ones ? ~0 : old) & o[0] & .. & o[n_pos - 1] & ~(o[n_pos] | .. | o[n - 1]) & the bits inside [doc_lo, doc_hi).  Every operand has a bitmap
+void launch_setop_words(hipStream_t st, const SetOperand* ops, uint32_t n_pos, uint32_t n, bool is_or, bool init_ones, uint32_t* scratch, uint64_t scratch_words, uint64_t base_word,
+                        uint64_t words, uint32_t bitmap_base, uint32_t doc_lo, uint32_t doc_hi);
+// bit `id` of the scratch bitmap cleared for each of the n ids (an operand's docs)
+void launch_setop_clear(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_t* scratch);
+// every id of `leader` (an operand's docs) against ops[0 .. n): it survives when all hold it (negate: when none does).  refine false: survivors
+// are or-ed into the zeroed scratch bitmap; true: the ids that do not survive are cleared from it
+void launch_setop_probe(hipStream_t st, const uint32_t* leader, uint32_t leader_len, const SetOperand* ops, uint32_t n, bool negate, bool refine, uint32_t bitmap_base,
+                        uint32_t* scratch);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

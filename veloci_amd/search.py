@@ -47,11 +47,15 @@ class DocSet:
     """A set of anchor ids staged on the index's GPU (`vq_docset`).  Attached to a request it restricts the search to the set's docs, exactly as
     a `filter` leaf whose hits are these ids would (and-ed with the request's own `filter`).  `ids`: a numpy array or sequence of non-negative
     ints (copied as uint32; any order, duplicates allowed), or a contiguous torch tensor of dtype int32 / uint32 on the index's device (read in
-    place, no host copy).  Immutable; any number of requests may share one, and a request keeps its set alive after `close()`."""
+    place, no host copy).  Immutable; any number of requests may share one, and a request keeps its set alive after `close()`.  Sets of one index
+    compose on the device: `a & b`, `a | b`, `a - b`, `~a`, `a.minus(*others)`, `DocSet.combine` / `all_of` / `any_of` each make a new DocSet."""
+
+    OPS = {"and": 0, "or": 1, "minus": 2, "not": 3}  # VQ_DOCSET_AND ...
 
     def __init__(self, index, ids):
         self.L = _lib.lib()
         self.h = None
+        self.index = index  # the operators need it
         on_device, keep = 0, None
         if type(ids).__module__.split(".")[0] == "torch":
             import torch
@@ -90,10 +94,60 @@ class DocSet:
         self = cls.__new__(cls)
         self.L = _lib.lib()
         self.h = None
+        self.index = index
         h = C.c_void_p()
         _lib.check(self.L.vq_docset_from_filter(index.h, filter, len(filter), within._handle() if within is not None else None, C.byref(h)))
         self.h = h
         return self
+
+    @classmethod
+    def combine(cls, index, op, sets):
+        """Set algebra on the index's GPU (`vq_docset_combine`): `op` "and" / "or" over one or more DocSets of `index`, "minus" (sets[0] without the
+        ids of the others), "not" (one set: every anchor of the index's doc range outside it).  Any number of operands.  The result is an ordinary
+        DocSet; the operands are only read and may be closed afterwards.  On a shard the length is summed through `index.set_allreduce`'s hook."""
+        if op not in cls.OPS:
+            raise ValueError('DocSet.combine: op must be "and", "or", "minus" or "not"')
+        sets = list(sets)
+        handles = (C.c_void_p * max(len(sets), 1))(*[s._handle() for s in sets])
+        self = cls.__new__(cls)
+        self.L = _lib.lib()
+        self.h = None
+        self.index = index
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_combine(index.h, cls.OPS[op], handles, len(sets), C.byref(h)))
+        self.h = h
+        return self
+
+    @classmethod
+    def all_of(cls, index, sets):
+        """the ids every one of `sets` holds"""
+        return cls.combine(index, "and", sets)
+
+    @classmethod
+    def any_of(cls, index, sets):
+        """the ids at least one of `sets` holds"""
+        return cls.combine(index, "or", sets)
+
+    def minus(self, *others):
+        """this set without the ids of any of `others`"""
+        return DocSet.combine(self.index, "minus", [self, *others])
+
+    def __and__(self, other):
+        return DocSet.combine(self.index, "and", [self, other]) if isinstance(other, DocSet) else NotImplemented
+
+    def __or__(self, other):
+        return DocSet.combine(self.index, "or", [self, other]) if isinstance(other, DocSet) else NotImplemented
+
+    def __sub__(self, other):
+        return DocSet.combine(self.index, "minus", [self, other]) if isinstance(other, DocSet) else NotImplemented
+
+    def __invert__(self):
+        return DocSet.combine(self.index, "not", [self])
+
+    @property
+    def route(self):
+        """vq_debug_docset_route: -1 no combine made the set, 0 the word route built it, 1 the probe route"""
+        return int(self.L.vq_debug_docset_route(self._handle()))
 
     def _handle(self):
         if not self.h:
@@ -125,6 +179,18 @@ class DocSet:
     def ids(self):
         """the set's ids inside the index's doc range, sorted and unique (numpy uint32)"""
         return self.part(0)
+
+    def ids_tensor(self):
+        """the same ids as a torch int32 tensor on the index's device (`vq_docset_ids`, device to device: no host copy)"""
+        import torch
+        h, n = self._handle(), self.local_len
+        dev = torch.device("cuda", self.index.device)
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            torch.cuda.current_stream(dev).synchronize()  # the library copies on a stream of its own: nothing of torch's may still use the memory
+            if int(self.L.vq_docset_ids(h, C.c_void_p(out.data_ptr()), n, 1)) != n:
+                raise VelociError(5, self.L.vq_last_error().decode() or "vq_docset_ids failed")
+        return out
 
     def timings(self):
         """(mark, count + scan, expand) in ms, recorded when the set was made with VQ_DOCSET_TIMING=1 in the environment; else None"""

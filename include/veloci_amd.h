@@ -457,6 +457,20 @@ int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const 
  * writes the best min(top, non-zero counts) entries, returns their number, -1 on failure. */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts);
 
+/* ---- the two merges every search ends in, alone on crafted key tables (tests/test_gpu_merge_kernels.py).  A key is
+ * (order-preserving f32 score bits << 32) | doc id, 0 = an empty slot; n_jobs >= 1 jobs with top_k[j] in 1 .. 1024 share ONE launch, job j's
+ * output at the exclusive prefix of top_k.  0; -1 on a device error; -2 — before the device is touched — for a null pointer, n_jobs,
+ * num_shards or an n_spans of 0, a top_k outside 1 .. 1024, more than 2^24 keys in all, a stride_pad that is no multiple of 8 (or above 2^20). */
+/* k_merge_spans.  Job j: n_spans[j] spans of top_k[j] keys, back to back in span_keys (as the scans leave them: a set per span, zeros behind
+ * it).  out_keys: sum(top_k) keys — job j's best top_k[j], sorted descending, zeros behind. */
+int vq_debug_merge_spans(const uint64_t* span_keys, const uint32_t* n_spans, const uint32_t* top_k, uint32_t n_jobs, uint64_t* out_keys);
+/* k_finalize.  num_shards partial buffers in the layout a batch uses (hits[n_jobs], counters[n_jobs], keys[sum(top_k)]; no histograms),
+ * `stride_pad` extra bytes between them (the strided merge of a chunked step).  shard_keys: shard-major, per shard the jobs' keys at the prefix
+ * of top_k; shard_hits: shard-major, one u64 per job.  out_ids / out_score_bits (f32 bit patterns): sum(top_k) entries, job j's ranked window at
+ * the prefix of top_k, out_n[j] of them real; out_hits[j]: the shards' hit counts summed. */
+int vq_debug_finalize(const uint64_t* shard_keys, const uint64_t* shard_hits, uint32_t num_shards, size_t stride_pad, const uint32_t* top_k, uint32_t n_jobs,
+                      uint32_t* out_ids, uint32_t* out_score_bits, uint32_t* out_n, uint64_t* out_hits);
+
 /* ---- the pre-pass drivers alone (prepass.cpp run_union_jobs / run_locality_jobs / run_range_jobs / run_boost1n_jobs): what a batch runs before its
  * scans, on jobs the caller describes the way the request compiler does, with every list the drivers build copied back whole.  Jobs are passed as a
  * CSR: job j owns ids[job_off[j] .. job_off[j + 1]) (job_off[0] == 0, at most 2^31 ids, n_jobs >= 1) and names its stores by the paths they were

@@ -1447,6 +1447,25 @@ def test_random_requests_over_three_shards_match_the_oracle(corpus):
     _random_synthetic(corpus, n_requests=160, seed=int(os.environ.get("VQ_TEST_SEED", "3003")), shards=3)
 
 
+def test_and_or_and_single_requests_over_eight_shards_match_the_oracle(corpus):
+    """Eight doc-range shards — the shape of the multi-GPU runs — in one batch of AND, OR and single-leaf requests: with top + skip of 300
+    and 1000 k_finalize prunes inside its shard loop (8 x 300 and 8 x 1000 keys do not fit its buffer), with 1 and 64 it does not; one
+    request reaches beyond one scan's ranking and pages.  Ties the crafted partial layout of tests/test_gpu_merge_kernels.py to the real one."""
+    from veloci_amd import synth
+    from parity import assert_same
+    data, meta, idx, ora = corpus
+    a, b = list(meta.triples[0]), list(meta.triples[1])
+    shapes = [synth.req_and(a), synth.req_or(a), synth.req_single(meta.extra_probes[1]), synth.req_and(b[:2]), synth.req_or(b), synth.req_single(meta.extra_probes[2])]
+    reqs = [dict(shape, top=top, skip=skip) for shape in shapes for top, skip in ((300, 0), (700, 300), (1, 0), (64, 0))]
+    reqs.append(dict(synth.req_or(a), top=1500, skip=0))  # deep: its first page ranks 1024
+    wants = [ora.search_json(json.dumps(r)) for r in reqs]
+    assert len(wants[-1].ids) == 1500 and max(len(w.ids) for w in wants[:-1]) == 700 and min(w.num_hits for w in wants) >= 1
+    got = _search_batch_over_shards(data, reqs, 8)
+    for r, g, w in zip(reqs, got, wants):
+        assert not isinstance(g, Exception), (str(g), json.dumps(r))
+        assert_same(r, g, w)
+
+
 def _search_batch_over_shards(data, reqs, shards):
     """The index cut into `shards` doc ranges on one GPU; the shards run in threads and sum the few numbers some requests need over
     all shards (vq_index_set_allreduce); partial buffers are gathered and merged."""

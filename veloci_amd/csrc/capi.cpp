@@ -366,6 +366,42 @@ int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t to
     if (!hist || !out_values || !out_counts) return -1;
     return vq::debug_facet_select(hist, num_values, top, misalign, out_values, out_counts);
 }
+/* self-checks (tests): k_merge_spans / k_finalize alone on crafted key tables, all jobs in one launch.  0; -1 on a device error; -2 for
+   arguments outside the documented ranges, decided before the device is touched */
+static bool debug_merge_jobs_ok(const uint32_t* top_k, const uint32_t* n_spans, uint32_t n_jobs, uint64_t tables, uint64_t* keys_out) {
+    if (!top_k || !n_jobs || !tables) return false;
+    uint64_t keys = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        if (top_k[j] == 0 || top_k[j] > uint32_t(vq::kMaxTopK) || (n_spans && n_spans[j] == 0)) return false;
+        keys += uint64_t(n_spans ? n_spans[j] : 1) * top_k[j] * tables;
+        if (keys > (uint64_t(1) << 24)) return false;
+    }
+    *keys_out = keys;
+    return true;
+}
+int vq_debug_merge_spans(const uint64_t* span_keys, const uint32_t* n_spans, const uint32_t* top_k, uint32_t n_jobs, uint64_t* out_keys) {
+    uint64_t keys = 0;
+    if (!span_keys || !n_spans || !out_keys || !debug_merge_jobs_ok(top_k, n_spans, n_jobs, 1, &keys)) return -2;
+    try {
+        vq::debug_merge_spans(span_keys, n_spans, top_k, n_jobs, out_keys);
+    } catch (const std::exception&) {
+        return -1;
+    }
+    return 0;
+}
+int vq_debug_finalize(const uint64_t* shard_keys, const uint64_t* shard_hits, uint32_t num_shards, size_t stride_pad, const uint32_t* top_k, uint32_t n_jobs,
+                      uint32_t* out_ids, uint32_t* out_score_bits, uint32_t* out_n, uint64_t* out_hits) {
+    uint64_t keys = 0;
+    if (!shard_keys || !shard_hits || !out_ids || !out_score_bits || !out_n || !out_hits || stride_pad % 8 != 0 || stride_pad > (size_t(1) << 20) ||
+        !debug_merge_jobs_ok(top_k, nullptr, n_jobs, num_shards, &keys))
+        return -2;
+    try {
+        vq::debug_finalize(shard_keys, shard_hits, num_shards, stride_pad, top_k, n_jobs, out_ids, out_score_bits, out_n, out_hits);
+    } catch (const std::exception&) {
+        return -1;
+    }
+    return 0;
+}
 
 /* self-checks (tests): the pre-pass drivers of prepass.cpp alone — the jobs described as the compiler describes them, run by run_*_jobs, every
    job's whole (doc, f32) list copied back with its 8 sentinel entries.  0; -1 without a device (or when the driver fails); -2 for arguments

@@ -268,6 +268,20 @@ struct PartialLayout {
     uint64_t nq, total_keys, total_hist;
     uint64_t off_hits, off_stats, off_keys, off_hist, bytes;
 };
+// The one place the layout is computed: a batch's partial (exec.cpp) and the crafted partials of the merge self-checks (both in exec.cpp)
+inline PartialLayout partial_layout(uint64_t nq, uint64_t total_keys, uint64_t total_hist) {
+    const auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
+    PartialLayout lay{};
+    lay.nq = nq;
+    lay.total_keys = total_keys;
+    lay.total_hist = total_hist;
+    lay.off_hits = 0;
+    lay.off_stats = up(nq * 8, 16);
+    lay.off_keys = lay.off_stats + up(nq * 8, 16);
+    lay.off_hist = up(lay.off_keys + total_keys * 8, 256);  // == bytes of the all-gathered part
+    lay.bytes = up(lay.off_hist + total_hist * 4, 256);
+    return lay;
+}
 
 // 64-bit ranking key: (order-preserving f32 bits << 32) | doc  — larger == better under
 // (score desc, id desc) (search.rs:122-130).

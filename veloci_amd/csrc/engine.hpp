@@ -256,6 +256,11 @@ void run_highlight_batch(const Index& idx, const vqreq::RequestSearchPart* const
 // top_n texts sorted by (bits descending, text ascending) and the number of touched texts.  Throws without a device
 void debug_text_rank(const uint64_t* row_off, const uint32_t* vals, const uint32_t* bits, uint32_t num_rows, uint32_t num_texts, uint32_t top_n,
                      std::vector<std::pair<uint32_t, uint32_t>>& picked, uint32_t* touched);
+// k_merge_spans / k_finalize alone on crafted host tables, all jobs in one launch (vq_debug_merge_spans / vq_debug_finalize, which check the
+// arguments; include/veloci_amd.h describes the tables).  Throw without a device
+void debug_merge_spans(const uint64_t* span_keys, const uint32_t* n_spans, const uint32_t* top_k, uint32_t n_jobs, uint64_t* out_keys);
+void debug_finalize(const uint64_t* shard_keys, const uint64_t* shard_hits, uint32_t num_shards, size_t stride_pad, const uint32_t* top_k, uint32_t n_jobs,
+                    uint32_t* out_ids, uint32_t* out_score_bits, uint32_t* out_n, uint64_t* out_hits);
 // n suggest requests as one device batch (a null request, or one that fails, fails alone: status / errors); every result equals run_suggest's
 void run_suggest_batch(const Index& idx, const vqreq::Request* const* reqs, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,
                        std::vector<std::string>& errors);

@@ -612,15 +612,7 @@ static BatchLayout plan_layout(const Index& idx, PartialBatch& pb) {
     pb.total_facet_out = fac_out_total;
     pb.facet_jobs = std::move(jobs);
 
-    PartialLayout& lay = pb.layout;
-    lay.nq = L.nq;
-    lay.total_keys = L.total_keys;
-    lay.total_hist = L.total_hist;
-    lay.off_hits = 0;
-    lay.off_stats = align_up(size_t(L.nq) * 8, 16);
-    lay.off_keys = lay.off_stats + align_up(size_t(L.nq) * 8, 16);
-    lay.off_hist = align_up(lay.off_keys + size_t(L.total_keys) * 8, 256);  // == bytes of the all-gathered part
-    lay.bytes = align_up(lay.off_hist + size_t(L.total_hist) * 4, 256);
+    pb.layout = partial_layout(L.nq, L.total_keys, L.total_hist);
     return L;
 }
 
@@ -1240,6 +1232,80 @@ void debug_text_rank(const uint64_t* row_off, const uint32_t* vals, const uint32
     run_text_rank(false, ws, d_best, d_meta, nullptr, d_vals.as<uint32_t>(), num_texts, slots);
     picked = std::move(slot.picked);
     *touched = slot.touched;
+}
+
+// ---- the two merges alone (vq_debug_merge_spans / vq_debug_finalize): one zero-filled QHeader per job with only the fields the kernel reads,
+// ONE launch of the shipped launcher over all jobs.  The callers (capi.cpp) have checked the arguments
+namespace {
+// blobs + blob_off of the jobs' headers -> device; fill(j, header) sets job j's fields beside top_k and part_keys_off (the prefix of top_k)
+template <class Fill>
+void debug_upload_headers(DevBuf& d_blobs, DevBuf& d_blob_off, const uint32_t* top_k, uint32_t n_jobs, Fill fill) {
+    const size_t blob = align_up(sizeof(QHeader), 16);
+    std::vector<uint8_t> blobs(n_jobs * blob, 0);
+    std::vector<uint32_t> off(n_jobs);
+    uint32_t keys = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        QHeader H{};
+        H.top_k = top_k[j];
+        H.part_keys_off = keys;
+        keys += top_k[j];
+        fill(j, H);
+        off[j] = uint32_t(j * blob);
+        std::memcpy(blobs.data() + j * blob, &H, sizeof H);
+    }
+    d_blobs.alloc(blobs.size());
+    d_blobs.upload(blobs.data(), blobs.size());
+    d_blob_off.alloc(off.size() * 4);
+    d_blob_off.upload(off.data(), off.size() * 4);
+}
+void debug_download(void* dst, const DevBuf& src, size_t bytes) { VQ_HIP(hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost)); }
+}  // namespace
+
+void debug_merge_spans(const uint64_t* span_keys, const uint32_t* n_spans, const uint32_t* top_k, uint32_t n_jobs, uint64_t* out_keys) {
+    DevBuf d_blobs, d_blob_off, d_span, d_part;
+    size_t in_keys = 0, n_out = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) n_out += top_k[j];
+    debug_upload_headers(d_blobs, d_blob_off, top_k, n_jobs, [&](uint32_t j, QHeader& H) {
+        H.n_spans = n_spans[j];
+        H.keys_base = uint32_t(in_keys);
+        in_keys += size_t(n_spans[j]) * top_k[j];
+    });
+    d_span.alloc(in_keys * 8);
+    d_span.upload(span_keys, in_keys * 8);
+    d_part.alloc(n_out * 8);
+    VQ_HIP(hipMemset(d_part.p, 0xFF, n_out * 8));  // (not zero: a slot the kernel leaves alone shows)
+    launch_merge_spans(nullptr, n_jobs, d_blobs.as<uint8_t>(), d_blob_off.as<uint32_t>(), d_span.as<unsigned long long>(), d_part.as<unsigned long long>());
+    VQ_HIP(hipDeviceSynchronize());
+    debug_download(out_keys, d_part, n_out * 8);
+}
+
+void debug_finalize(const uint64_t* shard_keys, const uint64_t* shard_hits, uint32_t num_shards, size_t stride_pad, const uint32_t* top_k, uint32_t n_jobs,
+                    uint32_t* out_ids, uint32_t* out_score_bits, uint32_t* out_n, uint64_t* out_hits) {
+    DevBuf d_blobs, d_blob_off, d_gathered, d_ids, d_scores, d_n, d_hits;
+    size_t keys = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) keys += top_k[j];
+    const PartialLayout lay = partial_layout(n_jobs, keys, 0);
+    const size_t stride = size_t(lay.off_hist) + stride_pad;
+    std::vector<uint8_t> gathered(stride * num_shards, 0);
+    for (uint32_t s = 0; s < num_shards; ++s) {
+        std::memcpy(gathered.data() + s * stride + lay.off_hits, shard_hits + size_t(s) * n_jobs, size_t(n_jobs) * 8);
+        std::memcpy(gathered.data() + s * stride + lay.off_keys, shard_keys + size_t(s) * keys, keys * 8);
+    }
+    debug_upload_headers(d_blobs, d_blob_off, top_k, n_jobs, [](uint32_t, QHeader&) {});
+    d_gathered.alloc(gathered.size());
+    d_gathered.upload(gathered.data(), gathered.size());
+    const std::pair<DevBuf*, size_t> outs[] = {{&d_ids, keys * 4}, {&d_scores, keys * 4}, {&d_n, size_t(n_jobs) * 4}, {&d_hits, size_t(n_jobs) * 8}};
+    for (const auto& o : outs) {
+        o.first->alloc(o.second);
+        VQ_HIP(hipMemset(o.first->p, 0xFF, o.second));
+    }
+    launch_finalize(nullptr, n_jobs, d_blobs.as<uint8_t>(), d_blob_off.as<uint32_t>(), d_gathered.as<uint8_t>(), num_shards, stride, lay, d_ids.as<uint32_t>(),
+                    d_scores.as<float>(), d_n.as<uint32_t>(), d_hits.as<unsigned long long>());
+    VQ_HIP(hipDeviceSynchronize());
+    debug_download(out_ids, d_ids, keys * 4);
+    debug_download(out_score_bits, d_scores, keys * 4);
+    debug_download(out_n, d_n, size_t(n_jobs) * 4);
+    debug_download(out_hits, d_hits, size_t(n_jobs) * 8);
 }
 
 void run_highlight_batch(const Index& idx, const vqreq::RequestSearchPart* const* parts_in, size_t n, std::vector<std::vector<SuggestEntry>>& out, std::vector<int>& status,

@@ -1074,7 +1074,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_spans(const uint8_t* __
                     uint32_t base = 0;
                     if (lane == (uint32_t)__ffsll((long long)m) - 1u) base = atomicAdd(&fill[0], cnt);
                     base = (uint32_t)__shfl((int)base, __ffsll((long long)m) - 1);
-                    if (base + cnt > (uint32_t)kCandCap) fill[1] = 1u;  // (only when nearly all keys tie: take the general path below)
+                    if (base + cnt > (uint32_t)kCandCap) fill[1] = 1u;  // (a weak bound — nearly all keys tie, few hits per span, a subset of small keys only: take the general path below)
                     else if (keep) cand[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
                 }
             }

@@ -1714,9 +1714,32 @@ void bounded_wait(const Index& idx, ShardComm& c, hipEvent_t ev) {
     }
     (void)idx;
 }
-// The step's merge and download go onto the finish stream, behind its exchange.  The NEXT step's scans are ordered behind them (ev_fin): a
-// scan launch fills every wave slot of the chip at once, and a merge queued beside it would wait for slots to free up (measured: 0.8-1.5 ms
-// for a kernel that takes 8 us on an idle chip) — the GPU idles for the tens of microseconds of the exchange instead.
+// The scan stream of chunk k of a step.  Chunk 0: the index's.  Chunk 1 of an index that scans on its own stream: a second stream, so that the
+// chunk's upload, memset, scans and span merge are not ordered behind chunk 0's — the second launch's workgroups take the wave slots the first
+// one's tail leaves free, and chunk 0 of the NEXT step (behind chunk 0 of this one in stream order) does the same for this chunk's tail.  The
+// chunks share nothing on the device: each has the workspace of its slot (upload area, span keys, partial, events).
+// VQ_STEP_SCAN_STREAMS=1 (read once): every chunk on the index's scan stream.  A caller's stream (vq_index_set_stream/s) is never left.
+hipStream_t step_scan_stream(const Index& idx, size_t k) {
+    static const bool one = [] {
+        const char* e = std::getenv("VQ_STEP_SCAN_STREAMS");
+        return e && std::atoi(e) == 1;
+    }();
+    return k && !one && idx.stream == idx.own_stream && idx.own_stream2 ? idx.own_stream2 : idx.stream;
+}
+// Whether a step's scans are ordered behind the previous step's finalize and download (ev_fin).  On one scan stream they are: a scan launch fills
+// every wave slot of the chip at once, and a finalize queued beside it waits for slots to free up (measured: 0.8-1.5 ms for a kernel that takes
+// 8 us on an idle chip) — the GPU idles for the tens of microseconds of the exchange instead.  On two scan streams the wait would drain the chip
+// at every step boundary, which is what the second stream is there to avoid: stream order alone keeps chunk k of a step behind chunk k of the
+// step before.  VQ_STEP_FIN_WAIT=0 / 1 (read once) sets it for both cases.
+bool step_waits_for_finalize(bool two_streams) {
+    static const int knob = [] {
+        const char* e = std::getenv("VQ_STEP_FIN_WAIT");
+        return e ? int(std::atoi(e) != 0) : -1;
+    }();
+    return knob >= 0 ? knob != 0 : !two_streams;
+}
+// The step's finalize and download go onto the finish stream, behind its exchange and behind every chunk's scans and span merge (ev_done of the
+// chunk's workspace, recorded on the chunk's own scan stream).  Whether the NEXT step's scans are ordered behind them: step_waits_for_finalize.
 void step_queue_merge(vq_shard_step& step) {
     if (step.merge_queued) return;
     step.merge_queued = true;
@@ -1747,10 +1770,17 @@ int vq_shard_step_begin(const vq_index* index, const vq_request* const* requests
         const auto tb0 = std::chrono::steady_clock::now();
         VQ_HIP(hipSetDevice(idx.device));
         const std::vector<const Request*> reqs = request_pointers(requests, n);
-        if (c.unmerged) {  // the step before this one: its merge goes out first, this step's scans run behind it
+        // An index that answers alone, on its own streams: the second chunk of a step goes onto a scan stream of its own (step_scan_stream), and
+        // the step does not wait for the previous step's finalize (step_queue_merge).  With an exchange the step stays on one scan stream.
+        const hipStream_t second = exchange ? idx.stream : step_scan_stream(idx, 1);
+        const bool two_streams = second != idx.stream;
+        if (c.unmerged) {  // the step before this one: its merge goes out first, this step's scans are queued behind it
             vq_shard_step& prev = *static_cast<vq_shard_step*>(c.unmerged);
             step_queue_merge(prev);
-            VQ_HIP(hipStreamWaitEvent(idx.stream, c.ev_fin[prev.parity], 0));
+            if (step_waits_for_finalize(two_streams)) {
+                VQ_HIP(hipStreamWaitEvent(idx.stream, c.ev_fin[prev.parity], 0));
+                if (two_streams) VQ_HIP(hipStreamWaitEvent(second, c.ev_fin[prev.parity], 0));
+            }
         }
         const auto tb1 = std::chrono::steady_clock::now();
         if (c.live >= 2) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_shard_step_begin: two steps are in flight already (end one first)");
@@ -1781,7 +1811,7 @@ int vq_shard_step_begin(const vq_index* index, const vq_request* const* requests
         for (size_t k = 0; k < nchunks; ++k) {
             const size_t b = n * k / nchunks, e = n * (k + 1) / nchunks;
             step->first.push_back(b);
-            step->pbs.push_back(run_partial(idx, reqs.data() + b, e - b, step->parity * 2 + int(k)));
+            step->pbs.push_back(run_partial(idx, reqs.data() + b, e - b, step->parity * 2 + int(k), -1, k ? second : idx.stream));
         }
         tb2 = std::chrono::steady_clock::now();
         // ---- the exchange: behind the step's scans, on the collective stream.  Per chunk the part of its partial in front of the histograms

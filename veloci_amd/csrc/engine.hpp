@@ -612,6 +612,8 @@ struct Index {
     hipStream_t pre_stream = nullptr;  // dictionary scans, union / range / count pre-passes: every one ends in a host synchronisation, so they need no
                                        // ordering with the scan stream — and on their own stream the pre-passes of batch c+1 overlap the scan of batch c
     hipStream_t stream = nullptr;      // scans + span merges
+    hipStream_t own_stream2 = nullptr;  // the second chunk of a step that is cut in two, on an index that answers alone: its upload, scans and span
+                                        // merge go here, beside the first chunk's on `stream` (step_scan_stream, capi.cpp)
     hipStream_t fin_stream = nullptr;  // shard merge, facet selection, result download (== stream when the caller set one)
     mutable std::mutex profile_mutex;
     mutable Profile profile;
@@ -879,6 +881,7 @@ struct PartialBatch {
     const uint32_t* d_blob_off = nullptr;
     const FacetJob* d_facet_jobs = nullptr;
     uint8_t* d_partial = nullptr;
+    hipStream_t scan_stream = nullptr;  // where the batch's upload, scans and span merge are queued (the index's scan stream unless the caller named another)
     uint32_t total_spans = 0;
     uint32_t n_facet_jobs = 0;
     uint32_t total_facet_out = 0;
@@ -891,7 +894,8 @@ struct PartialBatch {
     ~PartialBatch();  // a batch given up before its merge waits for its scans: the workspace (pinned staging, blobs) is handed on only when the device is done with it
 };
 
-std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot = -1, int64_t arena_offset = -1);
+std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot = -1, int64_t arena_offset = -1,
+                                          hipStream_t scan_stream = nullptr);  // scan_stream null: the index's
 void finish_batch(const Index& idx, PartialBatch& pb, const void* gathered_device, uint32_t num_shards, std::vector<std::unique_ptr<Result>>& out,
                   std::vector<int>& status, std::vector<std::string>& errors, size_t shard_stride = 0);  // shard_stride: bytes between the shards'
                                                                                                          // copies in `gathered_device` (0: the partial's own size)

@@ -741,7 +741,7 @@ static ScanPlan pack_upload(const Index& idx, PartialBatch& pb, const BatchLayou
 static void launch_scans(const Index& idx, PartialBatch& pb, const BatchLayout& L, const ScanPlan& P, int64_t arena_offset) {
     Workspace& ws = *pb.ws;
     const PartialLayout& lay = pb.layout;
-    hipStream_t st = idx.stream;
+    hipStream_t st = pb.scan_stream;
     VQ_HIP(hipMemcpyAsync(ws.d_up.as<uint8_t>(), ws.h_up.as<uint8_t>(), P.up_bytes, hipMemcpyHostToDevice, st));
     ws.d_span_keys.ensure(size_t(L.total_span_keys) * 8 + 16);
     if (arena_offset >= 0) {  // a chunk of a sharded step with one collective: its partial lives in the index's arena
@@ -842,12 +842,13 @@ static void report_timing(size_t n, double t_start, const CompileReport& c, doub
                  v[0] * 1e-6, v[1] * 1e-6, (v[2] - v[1]) * 1e-6, v[3] * 1e-6, (double(v[5]) - double(v[0]) - double(v[2]) - double(v[3])) * 1e-6, v[4] * 1e-6);
 }
 
-std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot, int64_t arena_offset) {
+std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request* const* reqs, size_t n, int slot, int64_t arena_offset, hipStream_t scan_stream) {
     const double t_start = now_ms();
     auto pb = std::make_unique<PartialBatch>();
     pb->index = &idx;
     pb->reqs.assign(reqs, reqs + n);
     pb->t0 = std::chrono::steady_clock::now();
+    pb->scan_stream = scan_stream ? scan_stream : idx.stream;
     acquire_workspace(idx, *pb, slot);
     VQ_HIP(hipSetDevice(idx.device));
     Workspace& ws = *pb->ws;
@@ -855,7 +856,7 @@ std::unique_ptr<PartialBatch> run_partial(const Index& idx, const vqreq::Request
     ws.ev_used = 0;
     pb->profiled = idx.profile.enabled;
 
-    const CompileReport compiled = compile_batch(idx, ws, *pb, reqs, n, idx.stream);
+    const CompileReport compiled = compile_batch(idx, ws, *pb, reqs, n, pb->scan_stream);
     size_spans(pb->queries);
     const BatchLayout layout = plan_layout(idx, *pb);
     const double t_layout = now_ms();
@@ -1768,7 +1769,7 @@ void finish_launch(const Index& idx, PartialBatch& pb, const void* gathered_devi
     if (!gathered_device) num_shards = 1;
     ws.d_down.ensure(D.bytes);
     ws.h_down.ensure(D.bytes);
-    if (st != idx.stream) VQ_HIP(hipStreamWaitEvent(st, ws.ev_done, 0));
+    if (st != pb.scan_stream) VQ_HIP(hipStreamWaitEvent(st, ws.ev_done, 0));
     uint8_t* dd = ws.d_down.as<uint8_t>();
     const bool prof = pb.profiled;
     {

@@ -74,6 +74,7 @@ Index::~Index() {
     if (own_stream) (void)hipStreamDestroy(own_stream);
     if (own_fin_stream) (void)hipStreamDestroy(own_fin_stream);
     if (pre_stream) (void)hipStreamDestroy(pre_stream);
+    if (own_stream2) (void)hipStreamDestroy(own_stream2);
 }
 
 bool Index::is_anchor_identity(const std::string& textindex_path) const {
@@ -179,6 +180,7 @@ std::unique_ptr<Index> build_index(const IndexBuilder& b, int device) {
         VQ_HIP(hipStreamCreateWithPriority(&idx->own_fin_stream, hipStreamNonBlocking, hi));
     }
     VQ_HIP(hipStreamCreateWithFlags(&idx->pre_stream, hipStreamNonBlocking));
+    VQ_HIP(hipStreamCreateWithFlags(&idx->own_stream2, hipStreamNonBlocking));
     idx->stream = idx->own_stream;
     idx->fin_stream = idx->own_fin_stream;
     for (auto& w : idx->ws) {

@@ -239,6 +239,22 @@ const char* vq_result_facet_value(const vq_result*, size_t facet, size_t i);
 uint64_t vq_result_facet_count(const vq_result*, size_t facet, size_t i);
 /* serde_json rendering of the SearchResult (ids/scores/facets/why_found_terms/why_found_info), for diffing. */
 const char* vq_result_to_json(const vq_result*);
+/* The facet counts of a staged set: facets_json is what Request.facets holds ([{"field": .., "top": ..}, ...]).
+ * *out is an ordinary vq_result: num_hits = vq_docset_len, no hits, the facets as a search over exactly these docs reports them.
+ * The set's docs are counted on the device (one kernel for all fields, no scoring, no candidate pool); `top` up to 1024 is ranked there, `top: null`
+ * over more values and larger tops on the host: count descending, value id ascending, zero counts dropped.  Fields come back in request order, the
+ * same field twice gives two entries; a value id beyond the dictionary renders as "".  An empty set yields every field with an empty list, an empty
+ * (or null) facet list a result without facets.  Unknown fields, a missing dictionary and facet sources that are not staged decline exactly as a
+ * search with these facets does; VQ_ERR_JSON for text that does not parse, VQ_ERR_INVALID_ARGUMENT for a null argument or a set of another index.
+ * Synchronous; any number of threads may call concurrently, also on one set, which is only read.  VQ_NO_DOCSET_FACET_LDS=1 in the environment
+ * (read at every call) counts short histograms like long ones (through the counter cache instead of a whole histogram in LDS).  On a shard the
+ * local histograms are summed over the shards before ranking: one call of the hook of vq_index_set_allreduce with every field's counters as u64
+ * (every rank calls in the same order; none when the whole set is empty); without the hook a shard answers VQ_ERR_UNSUPPORTED.  An unsharded
+ * index never calls the hook. */
+int vq_docset_facets(const vq_index*, const vq_docset*, const char* facets_json, size_t len, vq_result** out);
+/* measurement: with VQ_DOCSET_TIMING=1 in the environment, the HIP event time (ms) of the count kernel of this thread's last vq_docset_facets;
+ * negative when none was launched or timed */
+float vq_debug_docset_facets_count_ms(void);
 /* `SearchResult.why_found_terms` (src/search/result/search_result.rs:21-25, filled at src/search.rs:186 when the request says
  * `why_found: true`): per text index path the matched dictionary terms, as JSON {"<path>": ["term", ...]} (thread-local string;
  * the reference's map and list orders are unspecified). */

@@ -843,6 +843,25 @@ uint64_t vq_docset_ids(const vq_docset* d, uint32_t* out, uint64_t cap, int out_
     if (guard([&] { n = vq::copy_docset_ids(*d->set, out, cap, out_on_device != 0); }) != VQ_OK) return 0;  // (the reason is in vq_last_error)
     return n;
 }
+int vq_docset_facets(const vq_index* index, const vq_docset* d, const char* facets_json, size_t len, vq_result** out) {
+    return guard([&] {
+        if (!index || !d || !facets_json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_facets: null argument");
+        *out = nullptr;
+        std::vector<vqreq::FacetRequest> facets;
+        try {
+            const vqjson::Value v = vqjson::parse(facets_json, len);
+            if (!v.is_null()) facets = vqreq::facets_from_json(v);  // (Request::facets is an Option: null is no facet)
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        const std::shared_ptr<const DocSet> set = d->set;  // held for the length of the call
+        auto res = vq::docset_facets(*index->idx, *set, facets);
+        auto* h = new vq_result();
+        h->r = std::move(*res);
+        *out = h;
+    });
+}
+float vq_debug_docset_facets_count_ms(void) { return vq::docset_facets_last_count_ms(); }
 int vq_debug_docset_route(const vq_docset* d) { return d ? d->set->route : -1; }
 uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
 uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }

@@ -2215,35 +2215,10 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         // facets (search.rs:188-206, facet.rs:31-73)
         if (req.facets)
             for (auto& fr : *req.facets) {
-                std::vector<std::string> steps = get_steps_to_anchor(fr.field);
-                std::string store_path;
-                if (steps.size() == 1) store_path = steps.front() + PARENT_TO_VALUE_ID;
-                else if (idx.kv.count(steps.back() + ANCHOR_TO_TEXT_ID)) store_path = steps.back() + ANCHOR_TO_TEXT_ID;
-                const KVStore& kv = store_path.empty() ? idx.composed_facet(steps) : kv_store(store_path);  // facet.rs:38-57 / :59-70
-                if (!kv.facet_csr) unsupported("facet source " + store_path + " is not staged as an anchor-keyed CSR");
-                auto dit = idx.dict.find(steps.back());
-                if (dit == idx.dict.end()) throw VelociError(ERR_FST_NOT_FOUND, "fst not found loaded in indices " + steps.back() + " ");
-                DFacet f{};
-                f.offsets = kv.csr_off.as<uint64_t>();
-                f.values = kv.csr_values.as<uint32_t>();
-                f.direct = kv.csr_direct.p ? kv.csr_direct.as<uint32_t>() : nullptr;
-                f.key_base = kv.csr_key_base;
-                f.num_keys = kv.csr_num_keys;
-                // value ids beyond the dictionary (texts longer than do_not_store_text_longer_than) are counted too and render as ""
-                f.num_values = std::max<uint32_t>(uint32_t(dit->second.terms.size()), kv.csr_num_keys ? kv.csr_max_value + 1 : 0);
-                // top: null reports every value that was counted (facet.rs:19-23 truncates only with Some(top))
-                const uint64_t want = fr.top ? std::min<uint64_t>(*fr.top, f.num_values) : f.num_values;
-                // k_facet_select ranks up to kMaxTopK entries per facet; beyond that the histogram itself goes to the host (finish_batch)
-                f.top = want > uint64_t(kMaxTopK) ? 0u : uint32_t(want);
-                cq.facets.push_back(f);
-                FacetOut fo;
-                fo.field = fr.field;
-                fo.dict_path = steps.back();
-                fo.top = f.top;
-                fo.host_top = want > uint64_t(kMaxTopK) ? uint32_t(want) : 0u;
-                fo.num_values = f.num_values;
-                cq.facet_out.push_back(fo);
-                cq.algorithmic_bytes += 4ull * f.num_values;
+                ResolvedFacet rf = resolve_facet(idx, fr);
+                cq.facets.push_back(rf.f);
+                cq.facet_out.push_back(std::move(rf.out));
+                cq.algorithmic_bytes += 4ull * rf.f.num_values;
             }
         cq.algorithmic_bytes += 8ull * cq.top_k;
 
@@ -2551,6 +2526,44 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
 };
 
 }  // namespace
+
+// One FacetRequest against the index (search.rs:188-206, facet.rs:31-73): what a search's facet stage and docset_facets count by
+ResolvedFacet resolve_facet(const Index& idx, const FacetRequest& fr) {
+    std::vector<std::string> steps = get_steps_to_anchor(fr.field);
+    std::string store_path;
+    if (steps.size() == 1) store_path = steps.front() + PARENT_TO_VALUE_ID;
+    else if (idx.kv.count(steps.back() + ANCHOR_TO_TEXT_ID)) store_path = steps.back() + ANCHOR_TO_TEXT_ID;
+    auto kv_store = [&](const std::string& path) -> const KVStore& {
+        auto it = idx.kv.find(path);
+        if (it == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path);
+        return it->second;
+    };
+    const KVStore& kv = store_path.empty() ? idx.composed_facet(steps) : kv_store(store_path);  // facet.rs:38-57 / :59-70
+    if (!kv.facet_csr) unsupported("facet source " + store_path + " is not staged as an anchor-keyed CSR");
+    auto dit = idx.dict.find(steps.back());
+    if (dit == idx.dict.end()) throw VelociError(ERR_FST_NOT_FOUND, "fst not found loaded in indices " + steps.back() + " ");
+    ResolvedFacet r;
+    DFacet& f = r.f;
+    f = DFacet{};
+    f.offsets = kv.csr_off.as<uint64_t>();
+    f.values = kv.csr_values.as<uint32_t>();
+    f.direct = kv.csr_direct.p ? kv.csr_direct.as<uint32_t>() : nullptr;
+    f.key_base = kv.csr_key_base;
+    f.num_keys = kv.csr_num_keys;
+    // value ids beyond the dictionary (texts longer than do_not_store_text_longer_than) are counted too and render as ""
+    f.num_values = std::max<uint32_t>(uint32_t(dit->second.terms.size()), kv.csr_num_keys ? kv.csr_max_value + 1 : 0);
+    // top: null reports every value that was counted (facet.rs:19-23 truncates only with Some(top))
+    const uint64_t want = fr.top ? std::min<uint64_t>(*fr.top, f.num_values) : f.num_values;
+    // k_facet_select ranks up to kMaxTopK entries per facet; beyond that the histogram itself goes to the host (finish_batch)
+    f.top = want > uint64_t(kMaxTopK) ? 0u : uint32_t(want);
+    FacetOut& fo = r.out;
+    fo.field = fr.field;
+    fo.dict_path = steps.back();
+    fo.top = f.top;
+    fo.host_top = want > uint64_t(kMaxTopK) ? uint32_t(want) : 0u;
+    fo.num_values = f.num_values;
+    return r;
+}
 
 // THE routing decision: the scan kernel a compiled query runs on, from its final simple_flags.  The order of the tests is the precedence.  Span
 // sizing and byte accounting (above) and the launch plan (run_partial) go by the result; nothing else derives a class from the flag bits.

@@ -702,6 +702,13 @@ struct FacetOut {
     uint32_t num_values = 0;
     uint32_t host_top = 0;  // > 0: more entries than k_facet_select ranks (kMaxTopK) — the job's histogram is downloaded and ranked on the host; `top` is 0 then
 };
+// One FacetRequest resolved against the index (compile.cpp): the steps to the anchor, the direct / anchor_to_text_id / composed store, the histogram's
+// length, top against kMaxTopK.  A search's facet stage and docset_facets share it, errors and declines included (f.hist_off / f.out_off: the caller's)
+struct ResolvedFacet {
+    DFacet f;
+    FacetOut out;
+};
+ResolvedFacet resolve_facet(const Index& idx, const vqreq::FacetRequest& fr);
 
 // ---- explain (src/search/result/explain.rs:2-21)
 struct ExplainRec {
@@ -864,6 +871,14 @@ struct Result {
     bool rerun_exact = false;  // k_scan_probe_or's short cut could not be confirmed (CompiledQuery::or_skip_bound): finish_batch runs the request again
     mutable std::string json;
 };
+
+// The facet counts of a staged set (docset_facets.cpp, docset_facets.hip): every requested field's values counted over the set's docs, ranked and
+// rendered as a search over exactly these docs reports them.  num_hits = ds.len, no hits; the fields in request order.  Synchronous, on the index's
+// stream; each call owns its scratch, the set is only read: any number of threads may call on one set.  On a shard the local histograms are summed
+// over the shards before ranking (Index::sum_over_shards; every rank calls in the same order), ERR_UNSUPPORTED without the hook
+std::unique_ptr<Result> docset_facets(const Index& idx, const DocSet& ds, const std::vector<vqreq::FacetRequest>& facets);
+// the last call's count kernel in ms (HIP events), recorded per thread when VQ_DOCSET_TIMING is set; negative: none was launched or timed
+float docset_facets_last_count_ms();
 
 struct PartialBatch {
     const Index* index = nullptr;

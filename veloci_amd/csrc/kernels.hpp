@@ -208,6 +208,26 @@ void launch_setop_clear(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_
 // are or-ed into the zeroed scratch bitmap; true: the ids that do not survive are cleared from it
 void launch_setop_probe(hipStream_t st, const uint32_t* leader, uint32_t leader_len, const SetOperand* ops, uint32_t n, bool negate, bool refine, uint32_t bitmap_base,
                         uint32_t* scratch);
+// ---- facet counts of a doc set (docset_facets.hip): the histograms of m facets over a staged set's local ids, with the counting semantics of the
+// scans' facet stage.  A facet's source is an anchor-keyed CSR (offsets u64 [num_keys + 1], values u32) or, for a scalar field, a direct array
+// (u32 [num_keys], 0xFFFFFFFF = no value); its counters are hist[hist_off, + num_values)
+struct DocsetFacetD {
+    const uint64_t* offsets;
+    const uint32_t* values;
+    const uint32_t* direct;  // non-null: read instead of offsets / values
+    uint32_t key_base, num_keys;
+    uint32_t num_values;
+    uint32_t hist_off;
+    uint32_t lds;  // 1: the LDS mode (num_values <= kDocsetFacetLdsValues), 0: the cache mode
+    uint32_t pad;
+};
+// Counters of a histogram that lives in LDS whole: 16 KB per workgroup of one wave, so 10 workgroups share a CU's 160 KB (2.5 waves per SIMD)
+constexpr uint32_t kDocsetFacetLdsValues = 4096;
+// docs: a set's sorted local ids (16-byte aligned, padded to a multiple of 4 entries), local_len of them; facets: m descriptors in device memory;
+// hist: zeroed.  One launch for all m facets; nothing is launched for an empty set or an empty facet list
+void launch_docset_facet_count(hipStream_t st, const uint32_t* docs, uint32_t local_len, const DocsetFacetD* facets, uint32_t m, uint32_t* hist);
+// the top entries of the counted histograms: launch_facet_select's kernels and arguments
+void launch_docset_facet_rank(hipStream_t st, uint32_t n_jobs, const FacetJob* jobs, const uint32_t* hist, uint32_t* out_vals, uint32_t* out_counts, uint32_t* out_n);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

@@ -334,6 +334,25 @@ inline SearchRequest search_request_from_json(const vqjson::Value& v) {
     return r;
 }
 
+// Request::facets (a value that is not null): Vec<FacetRequest>, also parsed on its own for vq_docset_facets
+inline std::vector<FacetRequest> facets_from_json(const vqjson::Value& f) {
+    if (!f.is_array()) json_fail("facets: expected a sequence");
+    std::vector<FacetRequest> out;
+    for (auto& e : f.arr) {
+        if (!e.is_object()) json_fail("FacetRequest: expected an object");
+        FacetRequest fr;
+        const vqjson::Value* fld = e.get("field");
+        if (!fld) json_fail("missing field `field`");
+        fr.field = j_string(*fld, "field");
+        if (const vqjson::Value* t = e.get("top"); t) {  // present: null -> None, number -> Some
+            if (t->is_null()) fr.top = std::nullopt;
+            else fr.top = j_usize(*t, "top");
+        }
+        out.push_back(fr);
+    }
+    return out;
+}
+
 inline Request request_from_json(const vqjson::Value& v) {
     if (!v.is_object()) json_fail("Request: expected an object");
     Request r;
@@ -357,23 +376,7 @@ inline Request request_from_json(const vqjson::Value& v) {
         for (auto& e : b->arr) out.push_back(search_part_from_json(e));
         r.boost_term = out;
     }
-    if (const vqjson::Value* f = v.get("facets"); f && !f->is_null()) {
-        if (!f->is_array()) json_fail("facets: expected a sequence");
-        std::vector<FacetRequest> out;
-        for (auto& e : f->arr) {
-            if (!e.is_object()) json_fail("FacetRequest: expected an object");
-            FacetRequest fr;
-            const vqjson::Value* fld = e.get("field");
-            if (!fld) json_fail("missing field `field`");
-            fr.field = j_string(*fld, "field");
-            if (const vqjson::Value* t = e.get("top"); t) {  // present: null -> None, number -> Some
-                if (t->is_null()) fr.top = std::nullopt;
-                else fr.top = j_usize(*t, "top");
-            }
-            out.push_back(fr);
-        }
-        r.facets = out;
-    }
+    if (const vqjson::Value* f = v.get("facets"); f && !f->is_null()) r.facets = facets_from_json(*f);
     if (const vqjson::Value* p = v.get("phrase_boosts"); p && !p->is_null()) {
         if (!p->is_array()) json_fail("phrase_boosts: expected a sequence");
         std::vector<RequestPhraseBoost> out;

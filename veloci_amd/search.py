@@ -192,6 +192,22 @@ class DocSet:
                 raise VelociError(5, self.L.vq_last_error().decode() or "vq_docset_ids failed")
         return out
 
+    def facet_result(self, facets):
+        """The facet counts of the set's docs (`vq_docset_facets`) as a SearchResult: `num_hits` = len(self), no hits, `facets` as a search over
+        exactly these docs reports them.  `facets`: what `Request.facets` holds, a list of dicts ({"field": .., "top": ..}) or JSON text.  Counted
+        on the index's GPU without a search; on a shard the counts are summed over the shards through `index.set_allreduce`'s hook."""
+        if not isinstance(facets, (str, bytes)):
+            facets = json.dumps(list(facets))
+        if isinstance(facets, str):
+            facets = facets.encode()
+        out = C.c_void_p()
+        _lib.check(self.L.vq_docset_facets(self.index.h, self._handle(), facets, len(facets), C.byref(out)))
+        return _take_result(self.L, out)
+
+    def facets(self, facets):
+        """-> {field: [(value, count)]}, the form of `SearchResult.facets` (None for an empty facet list); see `facet_result`"""
+        return self.facet_result(facets).facets
+
     def timings(self):
         """(mark, count + scan, expand) in ms, recorded when the set was made with VQ_DOCSET_TIMING=1 in the environment; else None"""
         a, b, c = C.c_float(), C.c_float(), C.c_float()

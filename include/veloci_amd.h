@@ -203,6 +203,28 @@ int vq_docset_from_filter(const vq_index*, const char* filter_json, size_t len, 
  * the hook a shard answers VQ_ERR_UNSUPPORTED.  An unsharded index never calls the hook. */
 enum { VQ_DOCSET_AND = 0, VQ_DOCSET_OR = 1, VQ_DOCSET_MINUS = 2, VQ_DOCSET_NOT = 3 };
 int vq_docset_combine(const vq_index*, int op, const vq_docset* const* sets, size_t n, vq_docset** out);
+/* The set of the docs whose numeric column values satisfy every clause, selected on the device.  ranges_json: a non-empty list of clauses,
+ *   [{"field": "price", "gte": 10, "lt": 100}, {"field": "rating", "missing": true, "gt": 4.5}, {"field": "tags[].rank", "lte": 3}]
+ * `field` names the column "<field>.boost_valid_to_value", resolved as a request's boosts resolve it.  At most one of gt / gte and one of lt / lte
+ * (a null bound counts as absent).  A present, non-NaN f32 value v satisfies `gte: b` exactly when (double)v >= b, b being the f64 the JSON number
+ * parses to, and likewise for the others: `lte: 0.1` does not select a stored float32(0.1), `gte: 0.1` does.  -0 equals +0, the infinities and the
+ * denormals are ordinary values, NaN satisfies no clause and counts as present.  A clause without bounds selects every present non-NaN value, a
+ * lower bound above the upper one nothing.  `missing` (default false): whether a doc without a value satisfies the clause.  A field without "[]":
+ * the column is keyed by doc, as a boost reads it (no value below key_base, behind the last key, or with the presence bit clear).  A field with
+ * "[]": the column is keyed by value id, a value belongs to the anchor in the first entry of its "<field>.value_id_to_anchor" row; the clause holds
+ * for a doc when any of its present values is inside the interval, with `missing` also when it has no present value.  Any number of clauses, also
+ * on one field; OR and NOT are vq_docset_combine's.  within: NULL, or a set of the same index that is and-ed in.  Two routes fill the result's
+ * bitmap: the stream route reads the columns over the doc range; the probe route — `within` carries no bitmap and no clause is 1:n — gathers the
+ * values of within's ids, so its cost follows the small set.  VQ_NO_RANGE_PROBE=1 in the environment (read at every call) sends everything through
+ * the stream route.  VQ_ERR_JSON for text that does not parse or a value of the wrong type (a bound that is not a number); VQ_ERR_INVALID_ARGUMENT
+ * for an empty list, a clause without `field`, gt with gte, lt with lte, an unknown key, a ".token_values" column (keyed by term ids), a `within`
+ * of another index; the search's VQ_ERR_INDEX_NOT_FOUND ("Did not found path in indices ...") for an unknown column or a 1:n field without its
+ * value_id_to_anchor store.  The result is an ordinary, immutable doc set.  Synchronous; any number of threads may call concurrently.  On a shard
+ * the set's length is the sum over the shards: one u64 goes through the hook of vq_index_set_allreduce (every rank calls in the same order);
+ * without the hook a shard answers VQ_ERR_UNSUPPORTED.  An unsharded index never calls the hook. */
+int vq_docset_from_ranges(const vq_index*, const char* ranges_json, size_t len, const vq_docset* within, vq_docset** out);
+/* self-check (tests): -1 for a set not made from ranges, 0 when the stream route built it, 1 when the probe route did */
+int vq_debug_docset_range_route(const vq_docset*);
 /* The set's ids inside this index's doc range — sorted, unique, unpadded — to `out`: host memory, or with out_on_device != 0 device memory on the
  * index's GPU (4-byte aligned; copied device to device on the library's stream, finished when the call returns; the index must still exist).  At
  * most `cap` ids are copied; returns the local length (0 with the reason in vq_last_error when the copy failed). */

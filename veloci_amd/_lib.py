@@ -25,7 +25,7 @@ SYMBOLS = [
     "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_debug_merge_spans", "vq_debug_finalize", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_debug_union_lists", "vq_debug_locality_lists",
     "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_version",
     "vq_docset_create", "vq_docset_from_filter", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
-    "vq_request_set_docset", "vq_docset_combine", "vq_docset_ids", "vq_debug_docset_route", "vq_docset_facets", "vq_debug_docset_facets_count_ms",
+    "vq_request_set_docset", "vq_docset_combine", "vq_docset_ids", "vq_debug_docset_route", "vq_docset_facets", "vq_debug_docset_facets_count_ms", "vq_docset_from_ranges", "vq_debug_docset_range_route",
 ]
 COMM_ID_BYTES = 128
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -171,6 +171,8 @@ def lib():
         "vq_debug_docset_route": (i, [vp]),
         "vq_docset_facets": (i, [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(vp)]),
         "vq_debug_docset_facets_count_ms": (C.c_float, []),
+        "vq_docset_from_ranges": (i, [vp, C.c_char_p, C.c_size_t, vp, C.POINTER(vp)]),
+        "vq_debug_docset_range_route": (i, [vp]),
     }
     for name, (rt, at) in sig.items():
         f = getattr(L, name)

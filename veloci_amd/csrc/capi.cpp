@@ -837,6 +837,23 @@ int vq_docset_combine(const vq_index* index, int op, const vq_docset* const* set
         *out = h;
     });
 }
+int vq_docset_from_ranges(const vq_index* index, const char* ranges_json, size_t len, const vq_docset* within, vq_docset** out) {
+    return guard([&] {
+        if (!index || !ranges_json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_from_ranges: null argument");
+        *out = nullptr;
+        std::vector<vq::RangeClause> clauses;
+        try {
+            clauses = vq::range_clauses_from_json(vqjson::parse(ranges_json, len));
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        auto set = vq::make_docset_from_ranges(*index->idx, clauses, within ? within->set : nullptr);
+        auto* h = new vq_docset();
+        h->set = std::move(set);
+        *out = h;
+    });
+}
+int vq_debug_docset_range_route(const vq_docset* d) { return d ? d->set->range_route : -1; }
 uint64_t vq_docset_ids(const vq_docset* d, uint32_t* out, uint64_t cap, int out_on_device) {
     if (!d) return 0;
     uint64_t n = 0;

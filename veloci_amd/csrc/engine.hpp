@@ -648,6 +648,7 @@ struct DocSet {
     uint64_t device_bytes = 0;
     float ms_mark = -1.0f, ms_count_scan = -1.0f, ms_expand = -1.0f;  // VQ_DOCSET_TIMING=1: HIP event times of the three stages of its construction
     int route = -1;                // combine_docsets: 0 the word route built it, 1 the probe route; -1: no combine made it
+    int range_route = -1;          // make_docset_from_ranges: 0 the stream route built it, 1 the probe route; -1: not made from ranges
     int device = 0;                // the index's GPU and the stream the set was built on (its index's: vq_docset_ids copies on it)
     hipStream_t stream = nullptr;
 };
@@ -669,6 +670,23 @@ std::shared_ptr<const DocSet> make_docset_from_program(const Index& idx, hipStre
 // On a shard len is summed over the shards (Index::sum_over_shards)
 enum { SETOP_AND = 0, SETOP_OR = 1, SETOP_MINUS = 2, SETOP_NOT = 3 };
 std::shared_ptr<const DocSet> combine_docsets(const Index& idx, int op, const std::vector<std::shared_ptr<const DocSet>>& sets);
+// The set of the docs whose column values satisfy every clause (docset_ranges.cpp, docset_ranges.hip).  A clause names the column
+// "<field>.boost_valid_to_value" — anchor-keyed, or for a field with "[]" keyed by value id and joined to the anchors through
+// "<field>.value_id_to_anchor" (a doc holds when any of its present values does) — and bounds it: a present, non-NaN f32 value v satisfies a bound b
+// exactly when (double)v compares so to b; NaN satisfies nothing and counts as present; `missing`: a doc without a value satisfies the clause.
+// `within` (null: none) is and-ed in.  Any number of clauses.  Synchronous; each call owns its scratch.  On a shard len is summed over the shards
+// (Index::sum_over_shards), ERR_UNSUPPORTED without the hook
+struct RangeClause {
+    std::string field;
+    bool has_lower = false, lower_open = false, has_upper = false, upper_open = false, missing = false;  // open: gt / lt
+    double lower = 0.0, upper = 0.0;
+};
+// the clause list of vq_docset_from_ranges: throws vqjson::ParseError for a value of the wrong type, ERR_INVALID_ARGUMENT for a list or clause the
+// interface refuses (empty list, no field, gt with gte, lt with lte, an unknown key)
+std::vector<RangeClause> range_clauses_from_json(const vqjson::Value& v);
+// [lo, hi] of range_key values a clause's bounds select, cut to [kRangeKeyMin, kRangeKeyMax]; lo > hi: nothing
+void range_clause_keys(const RangeClause& c, uint32_t* lo, uint32_t* hi);
+std::shared_ptr<const DocSet> make_docset_from_ranges(const Index& idx, const std::vector<RangeClause>& clauses, std::shared_ptr<const DocSet> within);
 // The set's local ids (sorted, unique, unpadded): min(local_len, cap) of them to `out`, host memory or (on_device) memory of the set's GPU — then
 // device to device on the set's stream, finished on return.  Returns local_len
 uint64_t copy_docset_ids(const DocSet& ds, uint32_t* out, uint64_t cap, bool on_device);

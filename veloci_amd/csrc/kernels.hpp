@@ -228,6 +228,41 @@ constexpr uint32_t kDocsetFacetLdsValues = 4096;
 void launch_docset_facet_count(hipStream_t st, const uint32_t* docs, uint32_t local_len, const DocsetFacetD* facets, uint32_t m, uint32_t* hist);
 // the top entries of the counted histograms: launch_facet_select's kernels and arguments
 void launch_docset_facet_rank(hipStream_t st, uint32_t n_jobs, const FacetJob* jobs, const uint32_t* hist, uint32_t* out_vals, uint32_t* out_counts, uint32_t* out_n);
+// ---- doc sets from numeric ranges (docset_ranges.hip): the scratch bitmap filled from column values.  A clause: a dense f32 column (bit patterns)
+// with an optional presence bitmap, keyed by doc (row = doc - key_base; no value: doc < key_base, row >= num_keys, presence bit clear), and a closed
+// interval [lo, hi] of range_key values, lo > hi: empty; a doc without a value holds when `missing` is set.  bitmap != 0: a 1:n clause resolved by
+// launch_range_scatter — `values` is its in-range bitmap and `present` its has-a-value bitmap (null: not wanted), both of the scratch bitmap's
+// shape (word doc >> 5); the clause holds for a doc in `values` or not in `present`.  A launch takes up to kRangeClauseTable clauses, a doc must
+// satisfy all of them; the caller runs longer lists in passes
+struct RangeClauseD {
+    const uint32_t* values;
+    const uint32_t* present;
+    uint32_t key_base, num_keys;
+    uint32_t lo, hi;
+    uint32_t missing, bitmap;
+};
+constexpr uint32_t kRangeClauseTable = 8;
+struct RangeClauseTable {
+    RangeClauseD c[kRangeClauseTable];
+};
+// The order-preserving key of an f32 bit pattern: the sign-flipped pattern with -0 folded onto +0.  key(-inf) = 0x007FFFFF <= the key of every
+// number <= key(+inf) = 0xFF800000; every NaN lies outside.  (constexpr: the host and the kernels share it)
+constexpr uint32_t range_key(uint32_t bits) { return bits == 0x80000000u ? 0x80000000u : (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
+constexpr uint32_t kRangeKeyMin = 0x007FFFFFu, kRangeKeyMax = 0xFF800000u;
+// scratch words (doc >> 5) of the 64-doc groups that touch [doc_lo, doc_hi) = ballots of "all n clauses hold and mask holds the doc", the bits
+// outside the range zero.  mask: null (all docs), or words with doc's bit in word (doc >> 5) - mask_word0; it may be `scratch` itself (and-into).
+// A group whose docs are all masked is not written: its words must be zero already.  doc_hi <= the anchors the scratch bitmap covers
+void launch_range_bits(hipStream_t st, const RangeClauseD* clauses, uint32_t n, const uint32_t* mask, uint32_t mask_word0, uint32_t* scratch, uint64_t scratch_words,
+                       uint32_t doc_lo, uint32_t doc_hi);
+// every id of `ids` (a set's docs: sorted, 16-byte aligned, padded to a multiple of 4 entries) against the n column clauses.  refine false: the ids
+// that satisfy all are or-ed into the zeroed scratch bitmap; true: the ids that do not are cleared from it
+void launch_range_probe(hipStream_t st, const uint32_t* ids, uint32_t len, const RangeClauseD* clauses, uint32_t n, bool refine, uint32_t* scratch);
+// a 1:n clause: `column` is keyed by value id, a value belongs to the anchor in the first entry of its row of the value_id_to_anchor table (a_off
+// u64 [a_num_keys + 1], a_vals; row r = value id a_key_base + r; empty rows belong to nobody).  in_bits: bit `anchor` set for every present value
+// inside the interval; has_bits (null: not wanted): for every present value.  Both zeroed, of the scratch bitmap's shape; anchors outside
+// [doc_lo, doc_hi) set nothing
+void launch_range_scatter(hipStream_t st, const RangeClauseD& column, const uint64_t* a_off, const uint32_t* a_vals, uint32_t a_key_base, uint32_t a_num_keys, uint32_t doc_lo,
+                          uint32_t doc_hi, uint32_t* in_bits, uint32_t* has_bits);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

@@ -101,6 +101,40 @@ class DocSet:
         return self
 
     @classmethod
+    def from_ranges(cls, index, ranges, within=None):
+        """The set of the docs whose numeric column values satisfy every clause (`vq_docset_from_ranges`), selected on the index's GPU.  `ranges`: a
+        non-empty list of dicts or JSON text, e.g. [{"field": "price", "gte": 10, "lt": 100}, {"field": "rating", "gt": 4.5, "missing": True}]:
+        `field` names the column `<field>.boost_valid_to_value`, at most one of gt / gte and one of lt / lte bound it, `missing` says whether a doc
+        without a value satisfies the clause.  A stored f32 value is compared as a float64 with the bound as given; NaN satisfies no clause.  A
+        field with "[]" holds when any of the doc's values does.  `within`: a DocSet of the same index that is and-ed in; one without a bitmap (a
+        short candidate list) is probed id by id, so the cost follows it.  OR and NOT are `combine`'s.  The result is an ordinary DocSet.  On a
+        shard the length is summed over the shards through `index.set_allreduce`'s hook."""
+        if not isinstance(ranges, (str, bytes)):
+            ranges = json.dumps(list(ranges), allow_nan=False)  # (JSON has no infinity: a bound beyond the floats goes in as text, e.g. 1e999)
+        if isinstance(ranges, str):
+            ranges = ranges.encode()
+        self = cls.__new__(cls)
+        self.L = _lib.lib()
+        self.h = None
+        self.index = index
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_from_ranges(index.h, ranges, len(ranges), within._handle() if within is not None else None, C.byref(h)))
+        self.h = h
+        return self
+
+    @classmethod
+    def from_range(cls, index, field, gte=None, gt=None, lte=None, lt=None, missing=False, within=None):
+        """`from_ranges` with one clause: DocSet.from_range(index, "price", gte=10, lt=100)"""
+        clause = {"field": field, "missing": bool(missing)}
+        clause.update({k: v for k, v in (("gte", gte), ("gt", gt), ("lte", lte), ("lt", lt)) if v is not None})
+        return cls.from_ranges(index, [clause], within=within)
+
+    @property
+    def range_route(self):
+        """vq_debug_docset_range_route: -1 the set was not made from ranges, 0 the stream route built it, 1 the probe route"""
+        return int(self.L.vq_debug_docset_range_route(self._handle()))
+
+    @classmethod
     def combine(cls, index, op, sets):
         """Set algebra on the index's GPU (`vq_docset_combine`): `op` "and" / "or" over one or more DocSets of `index`, "minus" (sets[0] without the
         ids of the others), "not" (one set: every anchor of the index's doc range outside it).  Any number of operands.  The result is an ordinary

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE — the device layer stubbed for the CPU sanitizer build (`make -C veloci_amd/csrc asan`, tests/test_host_asan.py): the HIP
 // runtime calls the host side makes are mapped to host memory, every kernel launcher throws (one exception, opt-in: with VQ_STUB_DICT_SCAN=1
 // exact / prefix dictionary probes are answered by a plain loop, see launch_dict_scan below).  What this build can run is everything in front of
-// the first launch: index staging (index.cpp), request parsing, query compilation (compile.cpp), the C ABI's argument handling — under
+// the first launch: index staging (index.cpp), request parsing, query compilation (compile.cpp, term_lookup.cpp), the C ABI's argument handling — under
 // AddressSanitizer + UndefinedBehaviorSanitizer.  Never linked into the product library.
 // With VQ_STUB_LAUNCH_LOG=<file> every launcher appends one JSON line to that file (tests/test_launch_plan_cpu.py): its name and scalar arguments; a
 // scan launcher also the span_base / qmap tables it was handed ("device" memory is host memory here) and which of its output pointers are set.

@@ -4,7 +4,9 @@ through compile, routing, table packing and the launch calls over a "device" who
 (tests/native/hip_stub.cpp).  The routing knobs are read once per process, so every environment leg is a run of its own.
 With VQ_LAUNCH_PLAN_BATCH=prepass (and VQ_STUB_DICT_SCAN=1: the stub answers prefix probes with a plain loop) a second batch runs instead, on the
 same corpus: requests that go round the pre-pass loop of compile_batch (exec.cpp; the runners it calls are in prepass.cpp) — dictionary scan, union job, count pre-pass — beside plain
-ones that are compiled once."""
+ones that are compiled once.
+With VQ_LAUNCH_PLAN_PROFILE=<file> (tests/test_compile_accounting_cpu.py) profiling is on, and every section's profile_json() is appended to
+that file: what the compiler accounted per kernel class, which the launch log does not show."""
 import json
 import os
 import sys
@@ -71,12 +73,15 @@ def mark(what):
 declined = []
 data, meta = synth.generate(spec, device="cpu")
 PREPASS = os.environ.get("VQ_LAUNCH_PLAN_BATCH") == "prepass"
+PROFILE = os.environ.get("VQ_LAUNCH_PLAN_PROFILE")
 if PREPASS:
     assert os.environ.get("VQ_STUB_DICT_SCAN") == "1"
 reqs = prepass_requests(meta) if PREPASS else requests(meta)
 for lo, hi in ((0, N), (0, N // 2), (N // 2, N)):
     idx = veloci_amd.Index(data, device=0, doc_lo=lo, doc_hi=hi)
     mark("docs [%d, %d)" % (lo, hi))
+    if PROFILE:
+        idx.profile_enable()
     if PREPASS and hi - lo != N:
         idx.set_allreduce(lambda values: None)  # the sums over the shards: the other shard adds nothing
     if hi - lo == N:
@@ -84,6 +89,9 @@ for lo, hi in ((0, N), (0, N // 2), (N // 2, N)):
     else:
         res = veloci_amd.PartialBatch(idx, [veloci_amd.Request(r) for r in reqs]).merge(None, 1, raise_on_error=False)
     declined.append([i for i, r in enumerate(res) if isinstance(r, Exception)])
+    if PROFILE:
+        with open(PROFILE, "a") as f:
+            f.write(json.dumps({"section": "docs [%d, %d)" % (lo, hi), "profile": idx.profile_json()}) + "\n")
     del idx
 assert all(d == ([] if PREPASS else [len(reqs) - 1]) for d in declined), declined
 print("LAUNCH_PLAN_DRIVER_OK " + json.dumps({"requests": len(reqs), "declined": declined}))

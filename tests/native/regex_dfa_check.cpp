@@ -1,5 +1,5 @@
 // TEST PROGRAM (tests/test_regex_dfa_cpu.py builds it with g++ -fsanitize=address,undefined next to veloci_amd/csrc/regex_dfa.cpp and runs it):
-// the pattern -> DFA compiler of the device regex route against its yardstick, std::wregex as Compiler::regex_candidates uses it.
+// the pattern -> DFA compiler of the device regex route against its yardstick, std::wregex as regex_candidates (term_lookup.cpp) uses it.
 //   1. seeded random patterns from the supported grammar (every operator, groups nested to depth 3, repeats bounded so that the state cap is out
 //      of reach) x random terms of 0..20 code points over three alphabets (ASCII; Latin-1 + Greek; one with code points above U+FFFF), for
 //      ignore_case x starts_with: walking the DFA must agree with regex_match of `[\s\S]*?(?:pattern)` / regex_search of the pattern.

@@ -14,7 +14,7 @@ def _bits(a):
 def test_union_reference_matches_the_oracle_on_a_prefix_leaf():
     """resolve_token_to_anchor (search_field.rs:419-464): a `starts_with` leaf over 300 terms of mixed lengths under one prefix; the oracle's
     (id, score bits) of ALL hits equal the union reference with term scores default_score_for_distance(Levenshtein distance of term and prefix
-    = the extra letters, prefix_matches = true) — what the product's host code (compile.cpp scoring_distance) hands k_union."""
+    = the extra letters, prefix_matches = true) — what the product's host code (term_lookup.cpp scoring_distance) hands k_union."""
     import widecorpus
     from oracle import binding as O
     rng = np.random.default_rng(17)

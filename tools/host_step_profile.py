@@ -1,10 +1,8 @@
 """Host cost of one step (vq_shard_step_begin / _end) on THIS machine (no GPU): the product's host side built against the stubbed device layer
 (tests/native/hip_stub.cpp) with VQ_STUB_NOOP_LAUNCH=1 — launches do nothing, "results" are garbage — runs compile, pack, the launch calls and the
 result assembly of 1024-request steps; VQ_TIMING prints where the time went.  A development aid; nothing here is a measurement of the product.
-    g++ -std=c++17 -O2 -fPIC -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o /tmp/libveloci_host.so \
-        veloci_amd/csrc/{index,compile,exec,hostpool,capi,regex_dfa}.cpp tests/native/hip_stub.cpp
-    (or `make -C veloci_amd/csrc hoststub`: veloci_amd/_host_stub/libveloci_host_stub.so, the same at -O1)
-    python tools/host_step_profile.py /tmp/libveloci_host.so [single|and|mix] [steps]"""
+    make -C veloci_amd/csrc hoststub
+    python tools/host_step_profile.py veloci_amd/_host_stub/libveloci_host_stub.so [single|and|mix] [steps]"""
 import os
 import sys
 import time

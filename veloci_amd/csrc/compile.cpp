@@ -4,142 +4,25 @@
 // (src/plan_creator/execution_plan.rs:91-534, plan_steps.rs:137-345) and the host-only bookkeeping of
 // search() (src/search.rs:143-228): leaf de-duplication, filter / boost / phrase wiring, term-id
 // bookkeeping for text locality, path algebra.  Everything that touches postings, scores or hit
-// lists is NOT done here — it is encoded for k_tile_scan.
+// lists is NOT done here — it is encoded for k_tile_scan.  The dictionary side of a leaf (which terms it matches, what they score) is
+// term_lookup.cpp; suggest, highlight and why_found_info are text_requests.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <regex>
 #include <set>
 
-#include "engine.hpp"
+#include "compile_internal.hpp"
+#include "term_lookup.hpp"
 #include "text.hpp"
 
 namespace vq {
-std::atomic<uint64_t> g_compile_ns[16];  // 0 lookup_terms, 1 resolve_boost_1n, 2 emit_boost_1n rest, 3 leaf lists, 4 the longest single compile_query, 5 total;
-                                         // inside 1: 6 value-id gather, 7 sort, 8 (anchor, value) pairs; 9 order check + layers of a resolved list
+std::atomic<uint64_t> g_compile_ns[16];  // (the slots: compile_internal.hpp)
 
 using namespace vqreq;
 
 namespace {
 
-bool ends_with(const std::string& s, const char* suf) {
-    size_t n = std::strlen(suf);
-    return s.size() >= n && std::memcmp(s.data() + s.size() - n, suf, n) == 0;
-}
-
-[[noreturn]] void unsupported(const std::string& what) {
-    throw VelociError(ERR_UNSUPPORTED, "unsupported on the MI355X query path: " + what);
-}
-
-// reference src/util.rs:147-162
-std::vector<std::string> get_steps_to_anchor(const std::string& path) {
-    std::vector<std::string> paths;
-    std::string current;
-    size_t start = 0;
-    while (true) {
-        size_t dot = path.find('.', start);
-        std::string part = path.substr(start, dot == std::string::npos ? std::string::npos : dot - start);
-        if (!current.empty()) current += ".";
-        current += part;
-        if (ends_with(part, "[]")) paths.push_back(current);
-        if (dot == std::string::npos) break;
-        start = dot + 1;
-    }
-    paths.push_back(path + TEXTINDEX);
-    return paths;
-}
-
-// search_field.rs:27-33
-float default_score_for_distance(uint8_t distance, bool prefix_matches) {
-    if (prefix_matches) return 2.0f / (std::log2(float(distance) + 1.0f) + 0.2f);
-    return 2.0f / (float(distance) + 0.2f);
-}
-
-bool cp_eq(uint32_t a, uint32_t b, bool ci) { return a == b || (ci && vqtext::lower_cp(a) == vqtext::lower_cp(b)); }
-
-// Distance the reference scores a dictionary hit with (search_field.rs:691-732): the scoring automaton is built
-// over the lower-cased term with transpositions at cost one; beyond its maximum it falls back to the plain
-// character Levenshtein distance in u8 (255 for strings of 255 bytes or more).
-uint8_t scoring_distance(const std::string& lower_hit, const std::string& lower_term, uint32_t dfa_max) {
-    if (lower_hit == lower_term) return 0;  // (both distances of equal strings: the exact-match leaf, the common case)
-    const auto h = vqtext::decode_utf8(lower_hit), t = vqtext::decode_utf8(lower_term);
-    const size_t n = h.size(), m = t.size(), w = m + 1;
-    std::vector<uint32_t> osa((n + 1) * w), lev((n + 1) * w);
-    for (size_t j = 0; j <= m; ++j) osa[j] = lev[j] = uint32_t(j);
-    for (size_t i = 1; i <= n; ++i) {
-        osa[i * w] = lev[i * w] = uint32_t(i);
-        for (size_t j = 1; j <= m; ++j) {
-            const uint32_t sub = h[i - 1] == t[j - 1] ? 0u : 1u;
-            lev[i * w + j] = std::min({lev[(i - 1) * w + j] + 1, lev[i * w + j - 1] + 1, lev[(i - 1) * w + j - 1] + sub});
-            uint32_t v = std::min({osa[(i - 1) * w + j] + 1, osa[i * w + j - 1] + 1, osa[(i - 1) * w + j - 1] + sub});
-            if (i > 1 && j > 1 && h[i - 1] == t[j - 2] && h[i - 2] == t[j - 1]) v = std::min(v, osa[(i - 2) * w + j - 2] + 1);
-            osa[i * w + j] = v;
-        }
-    }
-    if (osa[n * w + m] <= dfa_max) return uint8_t(osa[n * w + m]);
-    if (lower_hit.size() >= 255 || lower_term.size() >= 255) return 255;
-    return uint8_t(lev[n * w + m]);
-}
-
-// levenshtein_distance after the clamp of search_field.rs:285-287 (0 when absent; the empty-term error is raised by the compiler)
-uint32_t clamped_lev(const RequestSearchPart& p) {
-    if (!p.levenshtein_distance) return 0;
-    const size_t chars = vqtext::decode_utf8(vqtext::to_lower_utf8(p.terms.empty() ? std::string() : p.terms[0])).size();
-    if (chars == 0) return 0;
-    return std::min<uint32_t>(*p.levenshtein_distance, uint32_t(chars) - 1);
-}
-
-// expression.rs:48-95 — "x op y", x/y = $SCORE or a float
-void parse_expression(const std::string& expression, DColBoost& cb) {
-    struct Tok {
-        int kind;  // 0 score, 1 float, 2.. operators (2 div, 3 mul, 4 add, 5 sub)
-        float val;
-    };
-    std::vector<Tok> ops;
-    std::string current;
-    auto try_float = [](const std::string& s, float& out) {
-        if (s.empty()) return false;
-        char* end = nullptr;
-        out = std::strtof(s.c_str(), &end);
-        return end && *end == 0 && end != s.c_str();
-    };
-    for (char ch : expression) {
-        if (ch == ' ') {
-            float v;
-            if (try_float(current, v)) ops.push_back({1, v});
-            current.clear();
-        } else current.push_back(ch);
-        if (current == "+") ops.push_back({4, 0}), current.clear();
-        else if (current == "-") ops.push_back({5, 0}), current.clear();
-        else if (current == "/") ops.push_back({2, 0}), current.clear();
-        else if (current == "*") ops.push_back({3, 0}), current.clear();
-        else if (current == "$SCORE") ops.push_back({0, 0}), current.clear();
-    }
-    float v;
-    if (try_float(current, v)) ops.push_back({1, v});
-    if (ops.size() < 3 || ops[0].kind > 1 || ops[2].kind > 1 || ops[1].kind < 2)
-        throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"bad score expression " + expression + "\" ");
-    cb.expr_lkind = ops[0].kind;
-    cb.expr_lval = ops[0].val;
-    cb.expr_rkind = ops[2].kind;
-    cb.expr_rval = ops[2].val;
-    cb.expr_op = ops[1].kind == 2 ? EX_DIV : ops[1].kind == 3 ? EX_MUL : ops[1].kind == 4 ? EX_ADD : EX_SUB;
-}
-
-struct Leaf {  // PlanStepFieldSearchToTokenIds + its result (execution_plan.rs:16-44, plan_steps.rs:137-148)
-    const RequestSearchPart* part = nullptr;  // the request's own part (it outlives the compilation)
-    std::string key;                          // part->key(), built once
-    const PostingStore* store = nullptr;      // "<path>.to_anchor_id_score", looked up once
-    std::string path;  // with ".textindex"
-    bool get_scores = false, get_ids = false, store_term_id_hits = false;
-    bool return_term = false, return_term_lowercase = false, store_term_texts = false;  // execution_plan.rs:16-44
-    std::vector<std::pair<uint32_t, std::string>> terms;  // term id -> text (search_field.rs:347-353), ascending ids
-    bool computed = false;
-    std::vector<std::pair<uint32_t, float>> hits_scores;  // (term id, term score), ascending term id
-    std::vector<uint32_t> hits_ids;                        // term ids
-    std::map<uint32_t, ExplainRecs> explain;               // options.explain: the dictionary result's records per term id (search_field.rs:334-343)
-};
 // Ascending, duplicate-free — for id lists that can reach 10^5 entries per leaf (the value ids behind a prefix leaf's 1:n boost): a bitmap over
 // the ids' span when it is dense enough (one pass to mark, one to read back), LSD radix passes otherwise; short lists take std::sort.
 void sort_unique_u32(std::vector<uint32_t>& v) {
@@ -198,29 +81,42 @@ void sort_unique_u32(std::vector<uint32_t>& v) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 
-// VQ_TIMING: where request compilation spends its time (summed over threads, printed per batch by exec.cpp)
-struct PhaseTimer {
-    static bool on() {
-        static const bool v = std::getenv("VQ_TIMING") != nullptr;
-        return v;
-    }
-    int slot;
-    std::chrono::steady_clock::time_point t0;
-    explicit PhaseTimer(int s) : slot(s) {
-        if (on()) t0 = std::chrono::steady_clock::now();
-    }
-    ~PhaseTimer() {
-        if (!on()) return;
-        const uint64_t ns = uint64_t(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
-        g_compile_ns[slot] += ns;
-        if (slot == 5) {  // the longest single request: what bounds a parallel pass from below
-            uint64_t cur = g_compile_ns[4].load();
-            while (ns > cur && !g_compile_ns[4].compare_exchange_weak(cur, ns)) {
-            }
-        }
-    }
+// The knobs of the routing and sizing phases of Compiler::run (experiments, tests), read together once per process
+struct CompileKnobs {
+    uint32_t tile_words_max;       // VQ_TILE_WORDS_MAX (256): the widest k_tile_scan tile in words, a power of two in [64, 2048]
+    size_t tile_lds_bytes;         // VQ_TILE_LDS_KB (12)
+    uint64_t span_postings;        // VQ_SPAN_POSTINGS (0: the span length of the query's class)
+    uint64_t facet_span_postings;  // VQ_FACET_SPAN_POSTINGS (4096)
+    uint64_t probe_min_docs;       // VQ_PROBE_MIN_DOCS (40 M): shards below it keep k_scan_simple (detect_pure_simple)
+    bool no_probe, no_probe_or, probe_no_arr, no_union_cov, force_generic, no_leaf_f32;  // VQ_NO_PROBE ... VQ_NO_LEAF_F32: set, whatever the value
 };
-static bool part_explains(const RequestSearchPart& p) { return p.options && p.options->explain; }  // search_request.rs:182-184
+const CompileKnobs& knobs() {
+    static const CompileKnobs k = [] {
+        auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+        auto num = [](const char* name, uint64_t unset) {
+            const char* e = std::getenv(name);
+            return e ? uint64_t(std::atoll(e)) : unset;
+        };
+        CompileKnobs v{};
+        const char* e = std::getenv("VQ_TILE_WORDS_MAX");
+        const uint32_t words = e ? uint32_t(std::atoi(e)) : 256u;
+        v.tile_words_max = 64;
+        while (v.tile_words_max < words && v.tile_words_max < 2048) v.tile_words_max <<= 1;
+        e = std::getenv("VQ_TILE_LDS_KB");
+        v.tile_lds_bytes = size_t(e ? std::atoi(e) : 12) * 1024;
+        v.span_postings = num("VQ_SPAN_POSTINGS", 0);
+        v.facet_span_postings = num("VQ_FACET_SPAN_POSTINGS", 4096);
+        v.probe_min_docs = num("VQ_PROBE_MIN_DOCS", 40'000'000ull);
+        v.no_probe = set("VQ_NO_PROBE");
+        v.no_probe_or = set("VQ_NO_PROBE_OR");
+        v.probe_no_arr = set("VQ_PROBE_NO_ARR");
+        v.no_union_cov = set("VQ_NO_UNION_COV");
+        v.force_generic = set("VQ_FORCE_GENERIC");
+        v.no_leaf_f32 = set("VQ_NO_LEAF_F32");
+        return v;
+    }();
+    return k;
+}
 
 struct NodeInfo {
     std::string label;           // request.terms[0] carried by the node's result (set_op.rs:122,215,439)
@@ -239,23 +135,6 @@ struct CountReq {
     uint32_t node_id;
     int root_op;
 };
-
-// The two std::wregex objects of a regex leaf (the yardstick of both routes: their flags, the wrapper, their errors)
-static std::wstring regex_widen(const std::string& u8) {
-    std::wstring w;
-    for (uint32_t cp : vqtext::decode_utf8(u8)) w.push_back(wchar_t(cp));
-    return w;
-}
-static void regex_objects(const RequestSearchPart& p, std::wregex& whole, std::wregex& anywhere) {
-    try {
-        const auto flags = std::regex::ECMAScript | (p.ignore_case.value_or(true) ? std::regex::icase : std::regex::ECMAScript);
-        const std::wstring pat = regex_widen(p.terms[0]);
-        whole = std::wregex(L"[\\s\\S]*?(?:" + pat + L")", flags);
-        anywhere = std::wregex(pat, flags);
-    } catch (const std::regex_error& e) {
-        throw VelociError(ERR_INVALID_REQUEST, std::string("InvalidRequest: \"regex ") + e.what() + "\" ");
-    }
-}
 
 struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cache, localities: the pass's pre-pass results)
     const Index& idx;
@@ -355,190 +234,16 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             for (auto& q : r.tree.queries) flag_tree_texts(q);
     }
 
-    // Regex leaf (search_field.rs:72-83), a HOST fallback for the dictionary side only (the postings of the matched terms stay on the device):
-    // regex-automata 0.1.9's dense DFA walks the term's bytes, unanchored at the start (its builder acts as if the pattern began with
-    // `(?s:.)*?`), and the term is accepted when the walk ENDS in a match state; `starts_with` accepts once any prefix did.  Restated over code
-    // points with std::wregex (ECMAScript grammar: the common subset of the two syntaxes; case-insensitivity beyond ASCII follows the C locale).
-    std::vector<uint32_t> regex_candidates(const Dictionary& dict, const RequestSearchPart& p) {
-        std::wregex whole, anywhere;
-        regex_objects(p, whole, anywhere);
-        std::vector<uint32_t> out;
-        for (uint32_t id = 0; id < dict.terms.size(); ++id) {
-            const std::wstring w = regex_widen(dict.terms[id]);
-            if (p.starts_with ? std::regex_search(w, anywhere) : std::regex_match(w, whole)) out.push_back(id);
-        }
-        return out;
-    }
-
-    // get_term_ids_in_field (search_field.rs:277-398) — dictionary side only
-    void lookup_terms(const Index& idx, Leaf& l, bool get_scores, bool get_ids) {
-        PhaseTimer pt(0);
-        const RequestSearchPart& p = *l.part;
-        // (`snippet` / `snippet_info` are not looked at here: a search resolves token hits with resolve_token_hits_to_text_id_ids_only, plan_steps.rs:184 —
-        //  snippets are made by search_field::highlight alone, search_field.rs:243 = vq_highlight_json)
-        if (p.terms.empty()) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"terms is empty\" ");
-        l.path = p.path;
-        if (!ends_with(l.path, TEXTINDEX)) l.path += TEXTINDEX;
-        const std::string lower_term = vqtext::to_lower_utf8(p.terms[0]);
-        uint32_t lev = 0;
-        if (p.levenshtein_distance) {  // :285-287
-            const auto lower_cps = vqtext::decode_utf8(lower_term);
-            if (lower_cps.empty()) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"empty term with levenshtein_distance\" ");
-            lev = std::min<uint32_t>(*p.levenshtein_distance, uint32_t(lower_cps.size()) - 1);
-        }
-        auto dit = idx.dict.find(l.path);
-        if (dit == idx.dict.end()) throw VelociError(ERR_FST_NOT_FOUND, "field does not exist " + l.path + " (fst not found)");
-        const Dictionary& dict = dit->second;
-        const bool ci = p.ignore_case.value_or(true);  // search_field.rs:88
-        const bool query_ascii = vqtext::is_ascii(p.terms[0].data(), p.terms[0].size());
-        std::vector<uint32_t> query_cps;  // decoded when a comparison needs code points
-        std::vector<uint32_t> cand;
-        const FuzzyProbe* probe = nullptr;
-        const bool regex = p.is_regex;
-        const bool scan = !regex && (lev != 0 || p.starts_with);
-        if (regex) {  // match set from k_dict_regex when the batch's probes hold the leaf, else the host walk; scored on the host either way
-            const FuzzyProbe* fp = nullptr;
-            if (fuzzy) {
-                auto it = fuzzy->find(fuzzy_key(p));
-                if (it != fuzzy->end() && it->second.regex && it->second.answered && it->second.status == 0) fp = &it->second;
-            }
-            if (fp) cand = fp->matches;
-            else cand = regex_candidates(dict, p);
-        } else if (scan) {  // match set computed on the device before compilation (k_dict_scan), ascending == FST stream order
-            const FuzzyProbe* fp = nullptr;
-            if (fuzzy && topn_probes && p.top) {
-                // A top-n probe of a suggest batch: `matches` / `scores` are the FINAL buffer of the loop below, made by k_dict_topn over the
-                // same matches in the same order, and they pass through that loop unchanged.  The loop's cut needs size == top_n + 200 BEFORE a
-                // push, which at most top_n + 200 entries in all never reach; so worst_score never rises, nothing is skipped, and the stable
-                // sort behind the loop sees the very vector the full route would have built.
-                auto it = fuzzy->find(topn_key(p));
-                if (it != fuzzy->end() && it->second.top_n != 0) fp = &it->second;
-            }
-            if (fuzzy && !fp) {
-                auto it = fuzzy->find(fuzzy_key(p));
-                if (it != fuzzy->end()) fp = &it->second;
-            }
-            if (!fp) unsupported("levenshtein_distance > 0 / starts_with without a dictionary scan (internal)");
-            if (fp->status != 0) throw VelociError(fp->status, fp->error);
-            cand = fp->matches;
-            probe = fp;
-        } else if (ci) {
-            auto it = dict.lower_map.find(lower_term);
-            if (it != dict.lower_map.end()) cand = it->second;
-        } else {
-            auto it = std::lower_bound(dict.terms.begin(), dict.terms.end(), p.terms[0]);
-            if (it != dict.terms.end() && *it == p.terms[0]) cand.push_back(uint32_t(it - dict.terms.begin()));
-        }
-        const bool limit_result = p.top.has_value();  // :292
-        const size_t top_n_search = p.top.value_or(10) + p.skip.value_or(0);
-        float worst_score = -std::numeric_limits<float>::max();
-        const bool check_prefix = p.starts_with || lev != 0;  // :302
-        for (size_t ci_ = 0; ci_ < cand.size(); ++ci_) {  // ascending ids == FST stream order
-            const uint32_t id = cand[ci_];
-            if (!scan && !regex) {
-                const std::string& cand_term = dict.terms[id];
-                bool eq = true;
-                if (query_ascii && vqtext::is_ascii(cand_term.data(), cand_term.size())) {  // bytes are code points
-                    eq = cand_term.size() == p.terms[0].size();
-                    for (size_t i = 0; i < cand_term.size() && eq; ++i) eq = cp_eq(uint8_t(cand_term[i]), uint8_t(p.terms[0][i]), ci);
-                } else {
-                    const auto cps = vqtext::decode_utf8(cand_term);
-                    if (query_cps.empty() && !p.terms[0].empty()) query_cps = vqtext::decode_utf8(p.terms[0]);
-                    eq = cps.size() == query_cps.size();
-                    for (size_t i = 0; i < cps.size() && eq; ++i) eq = cp_eq(cps[i], query_cps[i], ci);
-                }
-                if (!eq) continue;
-            }
-            if (get_ids) l.hits_ids.push_back(id);
-            if (get_scores) {  // :304-354
-                float score;
-                if (probe) score = probe->scores[ci_];
-                else {
-                    const std::string lower_hit = vqtext::to_lower_utf8(dict.terms[id]);
-                    const bool prefix_matches = check_prefix && lower_hit.compare(0, lower_term.size(), lower_term) == 0 && lower_hit.size() >= lower_term.size();
-                    score = default_score_for_distance(scoring_distance(lower_hit, lower_term, lev), prefix_matches);
-                }
-                if (limit_result) {
-                    if (score < worst_score) continue;  // (:324-327 returns before the term text is recorded)
-                    if (!l.hits_scores.empty() && l.hits_scores.size() == top_n_search + 200) {  // sort.rs:24-34
-                        std::sort(l.hits_scores.begin(), l.hits_scores.end(), [](auto& a, auto& b) { return a.second == b.second ? a.first > b.first : a.second > b.second; });
-                        l.hits_scores.resize(top_n_search);
-                        // (top + skip == 0 keeps nothing: the reference panics on its empty vector; here the bound stays where it was and the
-                        // truncation behind the loop leaves no hit)
-                        if (!l.hits_scores.empty()) worst_score = l.hits_scores.back().second;
-                    }
-                }
-                l.hits_scores.push_back({id, score});
-                if (part_explains(p)) {  // :334-343 (kept for hits a later top-n cut drops again, as in the reference)
-                    ExplainRec e;
-                    e.kind = ExplainRec::LevenshteinScore;
-                    e.a = score;
-                    e.term_id = id;
-                    e.text = dict.terms[id];
-                    l.explain[id] = ExplainRecs{e};
-                }
-            }
-            if (l.return_term || l.store_term_texts)  // :347-353
-                l.terms.push_back({id, l.return_term_lowercase ? vqtext::to_lower_utf8(dict.terms[id]) : dict.terms[id]});
-        }
-        if (p.boost)  // :359-364
-            for (auto& h : l.hits_scores) h.second *= *p.boost;
-        if (limit_result) {  // :373-376 (the reference's sort is unstable: tie order is unspecified there)
-            std::stable_sort(l.hits_scores.begin(), l.hits_scores.end(), [](auto& a, auto& b) { return a.second > b.second; });
-            if (l.hits_scores.size() > top_n_search) l.hits_scores.resize(top_n_search);
-        }
-    }
-    // token_value (search_field.rs:391-395): add_boost (boost.rs:470-504) over the matched TERMS — the boost column is keyed by term id
-    // ("<path>.textindex.token_values.boost_valid_to_value", create/token_values_to_tokens.rs) and shapes the term scores before any
-    // posting is read.  Host arithmetic (glibc log10f / log2f, as the reference links them).
-    void apply_token_value(const RequestBoostPart& tv, Leaf& l) {
-        const std::string path = tv.path + TEXTINDEX + TOKEN_VALUES + BOOST_VALID_TO_VALUE;
-        auto bit = idx.boost.find(path);
-        if (bit == idx.boost.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path);
-        DColBoost cb{};
-        fill_boost_params(cb, tv);
-        for (auto& h : l.hits_scores) {
-            bool skip = false;
-            for (uint32_t s = 0; s < cb.nskip; ++s) skip = skip || std::fabs(cb.skip[s] - h.second) < 0.00001f;
-            float v;
-            if (skip || !bit->second.host_value(h.first, &v)) continue;
-            const float vp = v + cb.param;
-            float score = h.second;
-            switch (cb.fun) {  // apply_boost, boost.rs:283-377
-                case BF_LOG10: score *= std::log10(vp); break;
-                case BF_LOG2: score *= std::log2(vp); break;
-                case BF_MULTIPLY: score *= vp; break;
-                case BF_ADD: score += vp; break;
-                case BF_REPLACE: score = vp; break;
-                default: break;
-            }
-            if (cb.expr_op != EX_NONE) {
-                const float a = cb.expr_lkind == 0 ? v : cb.expr_lval, b = cb.expr_rkind == 0 ? v : cb.expr_rval;
-                score += cb.expr_op == EX_DIV ? a / b : cb.expr_op == EX_MUL ? a * b : cb.expr_op == EX_ADD ? a + b : a - b;
-            }
-            if (part_explains(*l.part)) {  // boost.rs:297-300, 371-374
-                ExplainRec e;
-                e.kind = ExplainRec::Boost;
-                if (cb.fun == BF_LOG10) {
-                    e.a = std::log10(vp);
-                    l.explain[h.first].push_back(e);
-                }
-                e.a = score;
-                l.explain[h.first].push_back(e);
-            }
-            h.second = score;
-        }
-    }
     Leaf& field_result(const RequestSearchPart& part) {
         Leaf& l = leaf(part);
         if (!l.computed) {
-            lookup_terms(idx, l, l.get_scores, l.get_ids);
+            lookup_terms(idx, fuzzy, topn_probes, l, l.get_scores, l.get_ids);
             if (l.store_term_id_hits && !l.hits_scores.empty()) {  // search_field.rs:379-383
                 std::vector<uint32_t> ids;
                 for (auto& h : l.hits_scores) ids.push_back(h.first);
                 term_id_hits[l.path][part.terms[0]] = ids;
             }
-            if (part.token_value) apply_token_value(*part.token_value, l);  // :391-395
+            if (part.token_value) apply_token_value(idx, *part.token_value, l);  // :391-395
             l.computed = true;
         }
         return l;
@@ -786,18 +491,6 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         push_op(ops, op, sp);
         info.emitted = true;
         return info;
-    }
-
-    void fill_boost_params(DColBoost& cb, const RequestBoostPart& b) {
-        cb.fun = b.boost_fun ? int32_t(*b.boost_fun) : BF_NONE;  // enum order matches BoostFun
-        cb.param = b.param.value_or(0.0f);
-        if (b.skip_when_score) {
-            if (b.skip_when_score->size() > size_t(kMaxSkipWhen)) unsupported("more than 4 skip_when_score values");
-            cb.nskip = uint32_t(b.skip_when_score->size());
-            for (size_t i = 0; i < b.skip_when_score->size(); ++i) cb.skip[i] = (*b.skip_when_score)[i];
-        }
-        cb.expr_op = EX_NONE;
-        if (b.expression) parse_expression(*b.expression, cb);
     }
 
     // matched terms -> text ids -> value ids of the 1:n object -> (anchor, boost value) of every boosted value id (boost.rs:432-468)
@@ -1944,17 +1637,11 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
     }
 
     // ------------------------------------------------------------ the whole request (search.rs:143-228)
-    void run() {
-        cq.lists.reserve(8);  // (the vectors of a typical request: one allocation each instead of a growth chain)
-        cq.ops.reserve(8);
-        cq.pres.reserve(8);
-        cq.pres_in.reserve(16);
-        by_address.reserve(8);
-        if (req.filter_only) return run_filter_only();
-        // (`select` itself is not looked at: search::search leaves the reading of the selected fields to to_documents, search.rs:63-103; together with
-        //  why_found it asks for why_found_info, :220-224 — complete_why_found_requests)
-        // (`suggest` is not looked at either: search::search reads search_req, search.rs:151-155; suggest_multi is vq_suggest_json)
-        if (!req.search_req) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"search_req is None, but is required in search\" ");
+    // The phases of run(), in its order.  The order is part of the result: the phases append to cq.lists, cq.ops and cq.cols, and what comes
+    // later stores indices into them.
+
+    // reads req.top / skip / key_upper; leaves cq.top, cq.skip, cq.key_upper, cq.deep and cq.top_k
+    void plan_page() {
         const uint64_t top64 = req.top.value_or(10), skip64 = req.skip.value_or(0);  // :146
         const uint64_t want = top64 + skip64 < top64 ? ~0ull : top64 + skip64;
         cq.top = uint32_t(std::min<uint64_t>(top64, kMaxTopK));
@@ -1966,7 +1653,10 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             cq.skip = 0;
         }
         cq.top_k = uint32_t(std::max<uint64_t>(uint64_t(cq.top) + cq.skip, 1));
+    }
 
+    // reads the request's trees and phrase boosts; leaves every search part in `cache` / `by_address` with its flags (nothing in cq)
+    void collect_leaves() {
         // collect_all_field_request_into_cache (execution_plan.rs:91-106), then the flags set during plan creation
         if (req.phrase_boosts)
             for (auto& el : *req.phrase_boosts) {
@@ -1983,25 +1673,30 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                 leaf(el.search1).get_ids = true;
                 leaf(el.search2).get_ids = true;
             }
+    }
 
-        {  // explain: the reference's set operations look at the flag of ONE operand's request (set_op.rs:120,384); supported when
-           // all leaves agree — request.explain, or a single leaf with options.explain (tests/all/tests.rs:348-364)
-            size_t leaves = 0, flagged = 0;
-            std::function<void(const SearchRequest&)> walk = [&](const SearchRequest& r) {
-                if (r.kind == SearchRequest::Search) {
-                    ++leaves;
-                    flagged += part_explains(r.part) ? 1 : 0;
-                } else
-                    for (auto& q : r.tree.queries) walk(q);
-            };
-            walk(*req.search_req);
-            if (flagged && flagged != leaves) unsupported("explain on a part of the query tree");
-            explain_on = flagged != 0;
-            if (explain_on && req.phrase_boosts)  // apply_boost_from_iter records a boost or not depending on where its look-ahead rests (boost.rs:213-228): on ALL hits
-                unsupported("explain with phrase_boosts");
-            if (explain_on) xplan = std::make_shared<ExplainPlan>();
-        }
+    // reads the explain flags of the score tree's leaves; leaves explain_on and an empty xplan (nothing in cq)
+    void decide_explain() {
+        // explain: the reference's set operations look at the flag of ONE operand's request (set_op.rs:120,384); supported when
+        // all leaves agree — request.explain, or a single leaf with options.explain (tests/all/tests.rs:348-364)
+        size_t leaves = 0, flagged = 0;
+        std::function<void(const SearchRequest&)> walk = [&](const SearchRequest& r) {
+            if (r.kind == SearchRequest::Search) {
+                ++leaves;
+                flagged += part_explains(r.part) ? 1 : 0;
+            } else
+                for (auto& q : r.tree.queries) walk(q);
+        };
+        walk(*req.search_req);
+        if (flagged && flagged != leaves) unsupported("explain on a part of the query tree");
+        explain_on = flagged != 0;
+        if (explain_on && req.phrase_boosts)  // apply_boost_from_iter records a boost or not depending on where its look-ahead rests (boost.rs:213-228): on ALL hits
+            unsupported("explain with phrase_boosts");
+        if (explain_on) xplan = std::make_shared<ExplainPlan>();
+    }
 
+    // reads req.filter, req.docset, req.search_req and req.boost; leaves cq.fops and cq.ops over cq.lists (cover lists flagged), returns the score root
+    NodeInfo compile_trees() {
         // filter tree (ids only), then the score tree
         uint32_t sp = 0;
         if (req.filter) {
@@ -2012,7 +1707,11 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         sp = 0;
         NodeInfo root = compile_node(*req.search_req, false, cq.ops, sp, req.boost.value_or(std::vector<RequestBoostPart>{}));
         for (uint32_t li : root.cover) cq.lists[li].flags |= LIST_COVER;
+        return root;
+    }
 
+    // reads req.boost; leaves the request-level boosts in cq.cols (their columns in col_store) and cq.n_top_cols
+    void add_column_boosts() {
         // anchor-level column boosts (execution_plan.rs:175-189, boost.rs:470-504)
         if (req.boost)
             for (auto& b : *req.boost) {
@@ -2030,188 +1729,213 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                 cq.algorithmic_bytes += 0;  // 4 B gather per hit, unknown until run time
             }
         cq.n_top_cols = uint32_t(cq.cols.size());
-        if (explain_on) {
-            xplan->root = root.ex_nodes.at(0);
-            xplan->cols = cq.cols;  // (the request-level boosts only: 1:n boosts are declined above)
-            uint32_t depth = 0, deepest = 0;
-            ex_emit(xplan->root, depth, deepest);
-            if (deepest > kExStack) unsupported("explain: more than " + std::to_string(kExStack) + " operands alive at once");
-            cq.explain_plan = xplan;
-        }
-        if (!cq.leaf_cols.empty()) {  // parameters of the OP_BOOST1N ops live behind the request-level boosts
-            if (cq.cols.size() + cq.leaf_cols.size() > 255) unsupported("more than 255 boosts in one query");
-            for (DOp& op : cq.ops)
-                if (op.kind == OP_BOOST1N) op.child_slot[0] = uint8_t(op.child_slot[0] + cq.n_top_cols);
-            cq.cols.insert(cq.cols.end(), cq.leaf_cols.begin(), cq.leaf_cols.end());
-        }
+    }
 
+    // reads xplan's nodes, the root's explain node and cq.cols (request-level boosts only at this point); leaves cq.explain_plan
+    void finish_explain_plan(const NodeInfo& root) {
+        if (!explain_on) return;
+        xplan->root = root.ex_nodes.at(0);
+        xplan->cols = cq.cols;  // (the request-level boosts only: 1:n boosts are declined above)
+        uint32_t depth = 0, deepest = 0;
+        ex_emit(xplan->root, depth, deepest);
+        if (deepest > kExStack) unsupported("explain: more than " + std::to_string(kExStack) + " operands alive at once");
+        cq.explain_plan = xplan;
+    }
+
+    // reads cq.leaf_cols (the parameters of the OP_BOOST1N ops); leaves them behind the request-level boosts in cq.cols, the ops' slots rebased
+    void append_leaf_cols() {
+        if (cq.leaf_cols.empty()) return;
+        if (cq.cols.size() + cq.leaf_cols.size() > 255) unsupported("more than 255 boosts in one query");
+        for (DOp& op : cq.ops)
+            if (op.kind == OP_BOOST1N) op.child_slot[0] = uint8_t(op.child_slot[0] + cq.n_top_cols);
+        cq.cols.insert(cq.cols.end(), cq.leaf_cols.begin(), cq.leaf_cols.end());
+    }
+
+    // reads req.phrase_boosts and the two leaves of each; leaves the phrase-pair lists in cq.lists and one DGroup per term pair in cq.groups
+    void add_phrase_boosts() {
         // phrase boosts (execution_plan.rs:202-262, plan_steps.rs:235-293, search_field.rs:247-275)
-        if (req.phrase_boosts) {
-            std::map<std::pair<std::string, std::string>, std::vector<uint32_t>> grouped;  // (term1, term2) -> lists
-            for (auto& pb : *req.phrase_boosts) {
-                Leaf& l1 = field_result(pb.search1);
-                Leaf& l2 = field_result(pb.search2);
-                if (pb.search1.path != pb.search2.path) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"phrase boost over two different paths\" ");
-                std::string path = pb.search1.path;
-                if (!ends_with(path, TEXTINDEX)) path += TEXTINDEX;
-                path += PHRASE_PAIR_TO_ANCHOR;
-                auto it = idx.phrase.find(path);
-                if (it == idx.phrase.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path);
-                const PhraseStore& store = it->second;
-                auto& lists = grouped[{pb.search1.terms[0], pb.search2.terms[0]}];
-                for (uint32_t t1 : l1.hits_ids)
-                    for (uint32_t t2 : l2.hits_ids) {
-                        auto key = std::make_pair(t1, t2);
-                        auto kit = std::lower_bound(store.keys.begin(), store.keys.end(), key);
-                        if (kit == store.keys.end() || *kit != key) continue;
-                        const size_t k = size_t(kit - store.keys.begin());
-                        HList h;
-                        h.d_docs = store.anchors.as<uint32_t>() + store.start[k];
-                        h.len = store.len[k];
-                        h.global_len = store.len[k];
-                        lists.push_back(add_list(h));
-                        cq.algorithmic_bytes += 4ull * h.len;
-                    }
-            }
-            // lists of one group must be contiguous for DGroup: re-emit them in group order
-            for (auto& [terms, lists] : grouped) {
-                if (lists.empty()) continue;
-                bool contiguous = true;
-                for (size_t i = 1; i < lists.size(); ++i) contiguous = contiguous && lists[i] == lists[i - 1] + 1;
-                uint32_t begin = lists[0];
-                if (!contiguous) {
-                    begin = uint32_t(cq.lists.size());
-                    for (uint32_t li : lists) {
-                        HList copy = cq.lists[li];
-                        cq.total_len -= copy.len;  // counted twice otherwise
-                        add_list(copy);
-                    }
-                    for (uint32_t li : lists) cq.lists[li].len = 0, cq.lists[li].d_docs = nullptr;
-                }
-                DGroup g{};
-                g.list_begin = uint16_t(begin);
-                g.list_count = uint16_t(lists.size());
-                g.mult = 5.0f;  // plan_steps.rs:270-272
-                cq.groups.push_back(g);
-            }
-        }
-
-        // boost_term (search.rs:176-178, boost.rs:89-195, 380-402)
-        if (req.boost_term)
-            for (auto& part : *req.boost_term) {
-                Leaf l;
-                l.part = &part;
-                lookup_terms(idx, l, false, true);
-                const float mult = part.boost.value_or(2.0f);  // boost.rs:393
-                for (uint32_t li : ids_to_anchor_lists(l, true)) {
-                    DTermBoost tb{};
-                    tb.list = uint16_t(li);
-                    tb.mult = mult;
-                    cq.tboosts.push_back(tb);
-                    cq.algorithmic_bytes += 4ull * cq.lists[li].len;
-                }
-            }
-
-        if (req.why_found && req.has_select) {  // search.rs:220-224, why_found.rs:20-31
-            if (idx.sharded()) unsupported("why_found with select on a shard (why_found_info joins the returned anchors to their texts: the caller's merged page may hold other shards' anchors)");
-            auto plan = std::make_shared<WhyFoundPlan>();
-            for (auto& [path, terms] : term_id_hits) {
-                std::vector<uint32_t>& all = (*plan)[path];
-                for (auto& [term, ids] : terms) all.insert(all.end(), ids.begin(), ids.end());
-                std::sort(all.begin(), all.end());
-                all.erase(std::unique(all.begin(), all.end()), all.end());
-            }
-            cq.why_found_plan = std::move(plan);
-        }
-        // text locality (search.rs:180-184, boost.rs:11-87)
-        if (req.text_locality)
-            for (auto& [path, terms] : term_id_hits) {
-                if (terms.size() <= 1) continue;  // boost.rs:36-39
-                const KVStore& t2t = kv_store(path + TOKENS_TO_TEXT_ID);
-                if (!idx.is_anchor_identity(path)) {
-                    // Text ids are not anchors (boost.rs:72-83): the K7 pre-pass (run_locality_jobs) gathers the terms' token -> text rows, counts
-                    // the texts, expands them to anchors and hands back one (anchor, smallest 2*c*c) list for the field
-                    const KVStore& t2a = kv_store(path + TEXT_ID_TO_ANCHOR);
-                    if (!t2t.text_csr || !t2a.d_row_len.p) unsupported("text_locality: " + path + " is not staged for the device pre-pass");
-                    LocalityJob job;
-                    job.t2t_path = path + TOKENS_TO_TEXT_ID;
-                    job.t2a_path = path + TEXT_ID_TO_ANCHOR;
-                    job.key = "loc|" + path;
-                    for (auto& [term, ids] : terms) {
-                        job.key += "|";
-                        for (uint32_t id : ids) {
-                            job.tokens.push_back(id);
-                            job.key += std::to_string(id) + ",";
-                        }
-                    }
-                    const LocalityJob* done = nullptr;
-                    if (localities) {
-                        auto it = localities->find(job.key);
-                        if (it != localities->end()) done = &it->second;
-                    }
-                    if (!done) {
-                        cq.locality_requests.push_back(std::move(job));  // compiled again after the job ran
-                        continue;
-                    }
-                    if (!done->len) continue;  // no text holds two of the terms' tokens (in this shard)
+        if (!req.phrase_boosts) return;
+        std::map<std::pair<std::string, std::string>, std::vector<uint32_t>> grouped;  // (term1, term2) -> lists
+        for (auto& pb : *req.phrase_boosts) {
+            Leaf& l1 = field_result(pb.search1);
+            Leaf& l2 = field_result(pb.search2);
+            if (pb.search1.path != pb.search2.path) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"phrase boost over two different paths\" ");
+            std::string path = pb.search1.path;
+            if (!ends_with(path, TEXTINDEX)) path += TEXTINDEX;
+            path += PHRASE_PAIR_TO_ANCHOR;
+            auto it = idx.phrase.find(path);
+            if (it == idx.phrase.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path);
+            const PhraseStore& store = it->second;
+            auto& lists = grouped[{pb.search1.terms[0], pb.search2.terms[0]}];
+            for (uint32_t t1 : l1.hits_ids)
+                for (uint32_t t2 : l2.hits_ids) {
+                    auto key = std::make_pair(t1, t2);
+                    auto kit = std::lower_bound(store.keys.begin(), store.keys.end(), key);
+                    if (kit == store.keys.end() || *kit != key) continue;
+                    const size_t k = size_t(kit - store.keys.begin());
                     HList h;
-                    h.d_docs = done->d_docs;
-                    h.d_scores = reinterpret_cast<const uint16_t*>(done->d_vals);
-                    h.len = done->len;
-                    h.global_len = done->len;
-                    h.flags = LIST_HAS_SCORES | LIST_F32;
-                    h.term_score = 1.0f;
-                    DLocField lf{};
-                    lf.list_begin = uint16_t(add_list(h));
-                    lf.list_count = kLocPrecomputed;
-                    cq.locf.push_back(lf);
-                    cq.algorithmic_bytes += 8ull * h.len;
-                    continue;
+                    h.d_docs = store.anchors.as<uint32_t>() + store.start[k];
+                    h.len = store.len[k];
+                    h.global_len = store.len[k];
+                    lists.push_back(add_list(h));
+                    cq.algorithmic_bytes += 4ull * h.len;
                 }
-                DLocField lf{};
-                lf.list_begin = uint16_t(cq.loc_idx.size());
-                uint32_t count = 0;
-                const PostingStore* same_ps = nullptr;  // identity column: token->text row t == docs of posting list t (checked when staged)
-                if (t2t.rows_equal_postings) {
-                    auto pit = idx.postings.find(path + TO_ANCHOR_ID_SCORE);
-                    if (pit != idx.postings.end()) same_ps = &pit->second;
+        }
+        // lists of one group must be contiguous for DGroup: re-emit them in group order
+        for (auto& [terms, lists] : grouped) {
+            if (lists.empty()) continue;
+            bool contiguous = true;
+            for (size_t i = 1; i < lists.size(); ++i) contiguous = contiguous && lists[i] == lists[i - 1] + 1;
+            uint32_t begin = lists[0];
+            if (!contiguous) {
+                begin = uint32_t(cq.lists.size());
+                for (uint32_t li : lists) {
+                    HList copy = cq.lists[li];
+                    cq.total_len -= copy.len;  // counted twice otherwise
+                    add_list(copy);
                 }
-                for (auto& [term, ids] : terms)
-                    for (uint32_t id : ids) {
-                        if (id < t2t.key_base || id - t2t.key_base >= t2t.num_keys) continue;
-                        const uint32_t r = id - t2t.key_base;
-                        if (t2t.host_off[r] == t2t.host_off[r + 1]) continue;
-                        HList h;
-                        if (same_ps && id < same_ps->num_tokens) {  // read the posting list's doc ids (and its bitmap image) instead of a second copy
-                            h.d_docs = same_ps->docs.as<uint32_t>() + same_ps->start[id];
-                            h.len = same_ps->len[id];
-                            if (!same_ps->bm_start.empty() && same_ps->bm_start[id] >= 0) {
-                                h.flags |= LIST_BITMAP;
-                                h.d_bitmap = same_ps->bitmaps.as<uint32_t>() + same_ps->bm_start[id];
-                                h.d_rank_dir = same_ps->rank_dir.as<uint32_t>() + same_ps->rd_start[id];
-                            }
-                        } else {
-                            h.d_docs = t2t.values.as<uint32_t>() + t2t.start[r];
-                            h.len = t2t.len[r];
-                        }
-                        h.global_len = t2t.host_off[r + 1] - t2t.host_off[r];
-                        uint32_t li = UINT32_MAX;
-                        for (uint32_t e = 0; e < cq.lists.size(); ++e)  // already a list of this query (the term's own posting leaf): share its tile bitmap
-                            if (cq.lists[e].d_docs == h.d_docs && cq.lists[e].inline_idx < 0 && cq.lists[e].len == h.len) {
-                                li = e;
-                                break;
-                            }
-                        if (li == UINT32_MAX) {
-                            li = add_list(h);
-                            cq.algorithmic_bytes += 4ull * h.len;
-                        }
-                        cq.loc_idx.push_back(uint16_t(li));
-                        ++count;
-                    }
-                lf.list_count = uint16_t(count);
-                cq.locf.push_back(lf);
+                for (uint32_t li : lists) cq.lists[li].len = 0, cq.lists[li].d_docs = nullptr;
             }
+            DGroup g{};
+            g.list_begin = uint16_t(begin);
+            g.list_count = uint16_t(lists.size());
+            g.mult = 5.0f;  // plan_steps.rs:270-272
+            cq.groups.push_back(g);
+        }
+    }
 
+    // reads req.boost_term; leaves the anchor lists of every part's terms in cq.lists and one DTermBoost per list in cq.tboosts
+    void add_term_boosts() {
+        // boost_term (search.rs:176-178, boost.rs:89-195, 380-402)
+        if (!req.boost_term) return;
+        for (auto& part : *req.boost_term) {
+            Leaf l;
+            l.part = &part;
+            lookup_terms(idx, fuzzy, topn_probes, l, false, true);
+            const float mult = part.boost.value_or(2.0f);  // boost.rs:393
+            for (uint32_t li : ids_to_anchor_lists(l, true)) {
+                DTermBoost tb{};
+                tb.list = uint16_t(li);
+                tb.mult = mult;
+                cq.tboosts.push_back(tb);
+                cq.algorithmic_bytes += 4ull * cq.lists[li].len;
+            }
+        }
+    }
+
+    // reads term_id_hits (what the leaves matched, per field); leaves cq.why_found_plan
+    void plan_why_found() {
+        if (!(req.why_found && req.has_select)) return;  // search.rs:220-224, why_found.rs:20-31
+        if (idx.sharded()) unsupported("why_found with select on a shard (why_found_info joins the returned anchors to their texts: the caller's merged page may hold other shards' anchors)");
+        auto plan = std::make_shared<WhyFoundPlan>();
+        for (auto& [path, terms] : term_id_hits) {
+            std::vector<uint32_t>& all = (*plan)[path];
+            for (auto& [term, ids] : terms) all.insert(all.end(), ids.begin(), ids.end());
+            std::sort(all.begin(), all.end());
+            all.erase(std::unique(all.begin(), all.end()), all.end());
+        }
+        cq.why_found_plan = std::move(plan);
+    }
+
+    // reads term_id_hits; leaves per field with two or more matched terms a DLocField in cq.locf (or a job in cq.locality_requests)
+    void add_text_locality() {
+        // text locality (search.rs:180-184, boost.rs:11-87)
+        if (!req.text_locality) return;
+        for (auto& [path, terms] : term_id_hits) {
+            if (terms.size() <= 1) continue;  // boost.rs:36-39
+            const KVStore& t2t = kv_store(path + TOKENS_TO_TEXT_ID);
+            if (!idx.is_anchor_identity(path)) add_precomputed_locality(path, terms, t2t);
+            else add_token_list_locality(path, terms, t2t);
+        }
+    }
+    // reads `localities` (the K7 pre-pass results); leaves the field's (anchor, value) list in cq.lists and a kLocPrecomputed entry in cq.locf, or asks for the job
+    void add_precomputed_locality(const std::string& path, const std::map<std::string, std::vector<uint32_t>>& terms, const KVStore& t2t) {
+        // Text ids are not anchors (boost.rs:72-83): the K7 pre-pass (run_locality_jobs) gathers the terms' token -> text rows, counts
+        // the texts, expands them to anchors and hands back one (anchor, smallest 2*c*c) list for the field
+        const KVStore& t2a = kv_store(path + TEXT_ID_TO_ANCHOR);
+        if (!t2t.text_csr || !t2a.d_row_len.p) unsupported("text_locality: " + path + " is not staged for the device pre-pass");
+        LocalityJob job;
+        job.t2t_path = path + TOKENS_TO_TEXT_ID;
+        job.t2a_path = path + TEXT_ID_TO_ANCHOR;
+        job.key = "loc|" + path;
+        for (auto& [term, ids] : terms) {
+            job.key += "|";
+            for (uint32_t id : ids) {
+                job.tokens.push_back(id);
+                job.key += std::to_string(id) + ",";
+            }
+        }
+        const LocalityJob* done = nullptr;
+        if (localities) {
+            auto it = localities->find(job.key);
+            if (it != localities->end()) done = &it->second;
+        }
+        if (!done) {
+            cq.locality_requests.push_back(std::move(job));  // compiled again after the job ran
+            return;
+        }
+        if (!done->len) return;  // no text holds two of the terms' tokens (in this shard)
+        HList h;
+        h.d_docs = done->d_docs;
+        h.d_scores = reinterpret_cast<const uint16_t*>(done->d_vals);
+        h.len = done->len;
+        h.global_len = done->len;
+        h.flags = LIST_HAS_SCORES | LIST_F32;
+        h.term_score = 1.0f;
+        DLocField lf{};
+        lf.list_begin = uint16_t(add_list(h));
+        lf.list_count = kLocPrecomputed;
+        cq.locf.push_back(lf);
+        cq.algorithmic_bytes += 8ull * h.len;
+    }
+    // reads the token -> text rows of the field's matched terms; leaves them in cq.lists (shared with a leaf's list where they are one), their indices in cq.loc_idx, a DLocField in cq.locf
+    void add_token_list_locality(const std::string& path, const std::map<std::string, std::vector<uint32_t>>& terms, const KVStore& t2t) {
+        DLocField lf{};
+        lf.list_begin = uint16_t(cq.loc_idx.size());
+        uint32_t count = 0;
+        const PostingStore* same_ps = nullptr;  // identity column: token->text row t == docs of posting list t (checked when staged)
+        if (t2t.rows_equal_postings) {
+            auto pit = idx.postings.find(path + TO_ANCHOR_ID_SCORE);
+            if (pit != idx.postings.end()) same_ps = &pit->second;
+        }
+        for (auto& [term, ids] : terms)
+            for (uint32_t id : ids) {
+                if (id < t2t.key_base || id - t2t.key_base >= t2t.num_keys) continue;
+                const uint32_t r = id - t2t.key_base;
+                if (t2t.host_off[r] == t2t.host_off[r + 1]) continue;
+                HList h;
+                if (same_ps && id < same_ps->num_tokens) {  // read the posting list's doc ids (and its bitmap image) instead of a second copy
+                    h.d_docs = same_ps->docs.as<uint32_t>() + same_ps->start[id];
+                    h.len = same_ps->len[id];
+                    if (!same_ps->bm_start.empty() && same_ps->bm_start[id] >= 0) {
+                        h.flags |= LIST_BITMAP;
+                        h.d_bitmap = same_ps->bitmaps.as<uint32_t>() + same_ps->bm_start[id];
+                        h.d_rank_dir = same_ps->rank_dir.as<uint32_t>() + same_ps->rd_start[id];
+                    }
+                } else {
+                    h.d_docs = t2t.values.as<uint32_t>() + t2t.start[r];
+                    h.len = t2t.len[r];
+                }
+                h.global_len = t2t.host_off[r + 1] - t2t.host_off[r];
+                uint32_t li = UINT32_MAX;
+                for (uint32_t e = 0; e < cq.lists.size(); ++e)  // already a list of this query (the term's own posting leaf): share its tile bitmap
+                    if (cq.lists[e].d_docs == h.d_docs && cq.lists[e].inline_idx < 0 && cq.lists[e].len == h.len) {
+                        li = e;
+                        break;
+                    }
+                if (li == UINT32_MAX) {
+                    li = add_list(h);
+                    cq.algorithmic_bytes += 4ull * h.len;
+                }
+                cq.loc_idx.push_back(uint16_t(li));
+                ++count;
+            }
+        lf.list_count = uint16_t(count);
+        cq.locf.push_back(lf);
+    }
+
+    // reads req.facets; leaves cq.facets and cq.facet_out, and closes cq.algorithmic_bytes with the result page
+    void add_facets() {
         // facets (search.rs:188-206, facet.rs:31-73)
         if (req.facets)
             for (auto& fr : *req.facets) {
@@ -2221,7 +1945,10 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                 cq.algorithmic_bytes += 4ull * rf.f.num_values;
             }
         cq.algorithmic_bytes += 8ull * cq.top_k;
+    }
 
+    // reads label_wanted, maybe_reqs and count_reqs (what the trees asked to have measured); leaves the final count_reqs
+    void settle_count_requests() {
         if (label_wanted) {  // some OR needs the label of a nested AND: that takes the sizes of the two-operand ANDs as well
             if (maybe_reqs.empty() && count_reqs.empty()) unsupported("OR over an operand whose term label is only known at run time (set_op.rs:143,439)");
             if (!idx.can_sum_over_shards())
@@ -2229,153 +1956,167 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             count_reqs.insert(count_reqs.end(), maybe_reqs.begin(), maybe_reqs.end());
         }
         if (2 * count_reqs.size() + 1 > 256) unsupported("more than 127 AND operands whose sizes must be measured first");
-        build_presence_program();
-        if (!count_reqs.empty())  // count pre-pass: every tile that holds a doc of any list is visited
-            for (auto& l : cq.lists) l.flags |= LIST_COVER;
-        {  // shape that the kernel scores without the interpreter: <= 4 single-list posting leaves under one AND/OR
-            const size_t n = cq.ops.size();
-            auto is_leaf1 = [&](const DOp& o) {
-                return o.kind == OP_LEAF && o.list_count == 1 && (cq.lists[o.list_begin].flags & LIST_HAS_SCORES) && !(cq.lists[o.list_begin].flags & LIST_F32);
-            };
-            if (n == 1 && is_leaf1(cq.ops[0])) cq.simple_n = 1;
-            else if (n >= 3 && n <= 5 && cq.ops[n - 1].kind != OP_LEAF && cq.ops[n - 1].nchild == n - 1) {
-                bool ok = true;
-                for (size_t i = 0; i + 1 < n; ++i) ok = ok && is_leaf1(cq.ops[i]);
-                if (ok) cq.simple_n = uint32_t(n - 1);
-            }
-            // OR whose operands all have their own term slot: order the leaves by slot, so that the kernels' slot loop
-            // (set_op.rs:169-186) is the plain left-to-right sum over the operands
-            if (cq.simple_n > 1 && cq.ops[n - 1].kind == OP_OR && cq.ops[n - 1].nslots == cq.simple_n) {
-                DOp& root = cq.ops[n - 1];
-                std::vector<std::pair<uint8_t, DOp>> leaves;
-                for (uint32_t k = 0; k < cq.simple_n; ++k) leaves.push_back({root.child_slot[k], cq.ops[k]});
-                std::stable_sort(leaves.begin(), leaves.end(), [](auto& x, auto& y) { return x.first < y.first; });
-                for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                    cq.ops[k] = leaves[k].second;
-                    root.child_slot[k] = leaves[k].first;
-                }
-            }
-        }
+    }
 
-        {  // pure simple queries run on k_scan_simple (fixed 8192-doc tiles)
-            static const bool force_generic = std::getenv("VQ_FORCE_GENERIC") != nullptr;
-            const bool pure = cq.simple_n && count_reqs.empty() && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
-                              cq.facets.empty() && uint64_t(idx.doc_hi) - idx.doc_lo >= 65536;
-            if (pure && !force_generic) {
-                uint32_t f = kSfSimple;
-                // An AND whose cover (sparsest operand) is ONE list with a tile directory (at least 1/4096 of the docs) and whose other operands
-                // all have bitmap images: k_scan_probe streams the cover's postings — as ids and scores, even when the cover has a bitmap
-                // image of its own — and tests their bits in the operands' LDS tiles (VQ_NO_PROBE=1: k_scan_simple instead).
-                // On shards below ~40 M docs k_scan_simple is still ahead (a span is then a few dozen tiles: the probe kernel's start-up, threshold
-                // warm-up and pipeline drain weigh more — 12.5 M docs: 1.13 against 1.55 ms per 1024 queries; 25 M: 2.18 / 2.47; 50 M: 4.34 / 4.19;
-                // 100 M: 8.5 / 7.2).  VQ_PROBE_MIN_DOCS moves the line (the tests put it at 0).
-                static const bool no_probe = std::getenv("VQ_NO_PROBE") != nullptr;
-                static const uint64_t probe_min_docs = std::getenv("VQ_PROBE_MIN_DOCS") ? uint64_t(std::atoll(std::getenv("VQ_PROBE_MIN_DOCS"))) : 40'000'000ull;
-                bool probe = !no_probe && cq.simple_n >= 2 && cq.ops[cq.simple_n].kind == OP_AND && uint64_t(idx.doc_hi) - idx.doc_lo >= probe_min_docs;
-                uint32_t arr_mask = 0;  // operands probed as 16-bit arrays (2 B per posting) instead of bitmap words (a bit per doc): the fewer bytes win
-                if (probe) {
-                    static const bool no_arr = std::getenv("VQ_PROBE_NO_ARR") != nullptr;
-                    uint32_t covers = 0;
-                    for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                        const HList& l = cq.lists[cq.ops[k].list_begin];
-                        if (l.flags & LIST_COVER) {
-                            ++covers;
-                            probe = probe && l.d_cov32;
-                        } else {
-                            const bool arr = l.d_arr16 && !no_arr && (!(l.flags & LIST_BITMAP) || uint64_t(l.len) * 16 < uint64_t(idx.doc_hi) - idx.doc_lo);
-                            if (arr) arr_mask |= 1u << k;
-                            probe = probe && (arr || (l.flags & LIST_BITMAP));
-                        }
-                    }
-                    probe = probe && covers == 1;
-                }
-                // An OR of 2 or 3 leaves with a term slot each whose sparsest operand has a tile-packed image and whose other operands are bitmap words, on an
-                // unsharded index: k_scan_probe_or counts the union from the words' set bits and scores only the docs that hold the cover (the
-                // sparsest operand) — a doc without it scores at most `or_skip_bound`, and finish_batch confirms that the request's k-th best key lies
-                // above that before the result is handed out (otherwise the request runs again with exact_routes_only).  Sharded: a rank's partial
-                // leaves for the exchange before the host sees it, so shards keep k_scan_simple.  VQ_NO_PROBE_OR=1 switches the route off.
-                static const bool no_probe_or = std::getenv("VQ_NO_PROBE_OR") != nullptr;
-                uint32_t or_cover = UINT32_MAX;
-                if (!probe && !no_probe && !no_probe_or && !req.exact_routes_only && cq.top_k >= 1 && cq.simple_n >= 2 && cq.simple_n <= 3 && cq.ops[cq.simple_n].kind == OP_OR &&
-                    cq.ops[cq.simple_n].nslots == cq.simple_n && !idx.sharded() && !(idx.comm && idx.comm->nranks > 1) && uint64_t(idx.doc_hi) - idx.doc_lo >= probe_min_docs) {
-                    for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                        const HList& l = cq.lists[cq.ops[k].list_begin];
-                        if (l.d_cov32 && (or_cover == UINT32_MAX || l.len < cq.lists[cq.ops[or_cover].list_begin].len)) or_cover = k;
-                    }
-                    double sum = 0.0, cnt = 0.0;
-                    for (uint32_t k = 0; k < cq.simple_n && or_cover != UINT32_MAX; ++k) {
-                        if (k == or_cover) continue;
-                        const HList& l = cq.lists[cq.ops[k].list_begin];
-                        if (!(l.flags & LIST_BITMAP) || (l.flags & LIST_F32) || l.max_raw >= 0x7C00 || !(l.term_score >= 0.0f)) {
-                            or_cover = UINT32_MAX;
-                            break;
-                        }
-                        const uint16_t h = l.max_raw;  // finite non-negative f16
-                        const int e = (h >> 10) & 31, m = h & 1023;
-                        const double a = e ? std::ldexp(1.0 + m / 1024.0, e - 15) : std::ldexp(m / 1024.0, -14);
-                        const double v = double(l.term_score) * (a / 100.0);
-                        if (v >= 0.00001 * (1.0 - 1e-5)) cnt += 1.0;  // (set_op.rs:180: a slot counts from 1e-5 on)
-                        sum += v;
-                    }
-                    if (or_cover != UINT32_MAX) {
-                        const HList& c = cq.lists[cq.ops[or_cover].list_begin];
-                        if (!(c.term_score > 0.0f) || c.max_raw >= 0x7C00) or_cover = UINT32_MAX;  // (the kernel's bound is taken over the cover's raw scores)
-                        else {
-                            const double b = sum * cnt * cnt * (1.0 + 1e-5);  // f32 rounding of the kernel's sums stays below the margin
-                            cq.or_skip_bound = b < 3.0e38 ? float(b) : std::numeric_limits<float>::infinity();
-                            if (cq.or_skip_bound < float(b)) cq.or_skip_bound = std::nextafter(cq.or_skip_bound, std::numeric_limits<float>::infinity());
-                            probe = true;
-                        }
-                    }
-                }
-                const bool or_probe = or_cover != UINT32_MAX && probe;
-                bool seq = false;
-                for (uint32_t k = 0; k < cq.simple_n && !probe; ++k) {
-                    const HList& l = cq.lists[cq.ops[k].list_begin];
-                    if ((l.flags & LIST_COVER) && (l.flags & LIST_BITMAP)) seq = true;
-                }
-                if (seq) f |= kSfSeq;
-                if (probe) {
-                    f |= kSfProbe | arr_mask << kSfArrayShift | (or_probe ? kSfProbeOr : 0u);
-                    cq.probe = DProbe{};
-                    for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                        const HList& l = cq.lists[cq.ops[k].list_begin];
-                        cq.probe.leaf[k] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
-                        if ((arr_mask >> k) & 1u) cq.probe_arr_gran = std::max(cq.probe_arr_gran, l.tile_most);
-                    }
-                }
-                for (uint32_t k = 0; k < cq.simple_n; ++k) {
-                    const HList& l = cq.lists[cq.ops[k].list_begin];
-                    const bool cover = or_probe ? k == or_cover : (l.flags & LIST_COVER) != 0;
-                    if (cover) f |= 1u << (kSfCoverShift + k);
-                    if ((l.flags & LIST_BITMAP) && (seq || !cover) && !((arr_mask >> k) & 1u)) f |= 1u << (kSfBitmapShift + k);
-                    if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (kSfPrefetchShift + k);
-                }
-                // a single leaf whose list has a tile-packed image: k_scan_union streams that (4 B per posting) instead of ids + scores (6 B)
-                static const bool no_union_cov = std::getenv("VQ_NO_UNION_COV") != nullptr;
-                if (cq.simple_n == 1 && !no_union_cov) {
-                    const HList& l = cq.lists[cq.ops[0].list_begin];
-                    if (l.d_cov32 && l.d_gdir && l.d_tile_dir && l.term_score > 0.0f && !(l.flags & LIST_F32) && l.inline_idx < 0) {
-                        f |= kSfUnionPacked;
-                        cq.probe = DProbe{};
-                        cq.probe.leaf[0] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
-                    }
-                }
-                cq.simple_flags = f;
+    // reads cq.ops and cq.lists; leaves cq.simple_n (0: not the shape) and, for an OR with a slot per operand, the leaves of cq.ops in slot order
+    void detect_simple() {
+        // shape that the kernel scores without the interpreter: <= 4 single-list posting leaves under one AND/OR
+        const size_t n = cq.ops.size();
+        auto is_leaf1 = [&](const DOp& o) {
+            return o.kind == OP_LEAF && o.list_count == 1 && (cq.lists[o.list_begin].flags & LIST_HAS_SCORES) && !(cq.lists[o.list_begin].flags & LIST_F32);
+        };
+        if (n == 1 && is_leaf1(cq.ops[0])) cq.simple_n = 1;
+        else if (n >= 3 && n <= 5 && cq.ops[n - 1].kind != OP_LEAF && cq.ops[n - 1].nchild == n - 1) {
+            bool ok = true;
+            for (size_t i = 0; i + 1 < n; ++i) ok = ok && is_leaf1(cq.ops[i]);
+            if (ok) cq.simple_n = uint32_t(n - 1);
+        }
+        // OR whose operands all have their own term slot: order the leaves by slot, so that the kernels' slot loop
+        // (set_op.rs:169-186) is the plain left-to-right sum over the operands
+        if (cq.simple_n > 1 && cq.ops[n - 1].kind == OP_OR && cq.ops[n - 1].nslots == cq.simple_n) {
+            DOp& root = cq.ops[n - 1];
+            std::vector<std::pair<uint8_t, DOp>> leaves;
+            for (uint32_t k = 0; k < cq.simple_n; ++k) leaves.push_back({root.child_slot[k], cq.ops[k]});
+            std::stable_sort(leaves.begin(), leaves.end(), [](auto& x, auto& y) { return x.first < y.first; });
+            for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                cq.ops[k] = leaves[k].second;
+                root.child_slot[k] = leaves[k].first;
             }
         }
+    }
 
-        {  // one materialised leaf, nothing else that shapes presence or score: k_scan_leaf_f32 streams the list (facets counted per entry)
-            static const bool off = std::getenv("VQ_FORCE_GENERIC") != nullptr || std::getenv("VQ_NO_LEAF_F32") != nullptr;
-            if (!off && !cq.simple_flags && count_reqs.empty() && cq.ops.size() == 1 && cq.ops[0].kind == OP_LEAF && cq.ops[0].list_count == 1 &&
-                (cq.lists[cq.ops[0].list_begin].flags & LIST_F32) && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
-                cq.facets.empty())  // (with facets the rich kernel is faster: its 64-hit rounds put less pressure on the histogram's hot counters
-                                    //  than every span adding at once — an LDS-privatised histogram would lift that)
-                cq.simple_flags = kSfLeafF32;
+    // ------------------------------------------------------------ routes (each leaves cq.simple_flags != 0 when it takes the query; run() asks them in order)
+    // reads the simple leaves' lists; returns whether an AND can run on k_scan_probe, arr_mask: the operands it reads as 16-bit arrays (the rest as bitmap words)
+    bool and_probe_operands(uint32_t& arr_mask) {
+        // An AND whose cover (sparsest operand) is ONE list with a tile directory (at least 1/4096 of the docs) and whose other operands
+        // all have bitmap images: k_scan_probe streams the cover's postings — as ids and scores, even when the cover has a bitmap
+        // image of its own — and tests their bits in the operands' LDS tiles (VQ_NO_PROBE=1: k_scan_simple instead).
+        // On shards below ~40 M docs k_scan_simple is still ahead (a span is then a few dozen tiles: the probe kernel's start-up, threshold
+        // warm-up and pipeline drain weigh more — 12.5 M docs: 1.13 against 1.55 ms per 1024 queries; 25 M: 2.18 / 2.47; 50 M: 4.34 / 4.19;
+        // 100 M: 8.5 / 7.2).  VQ_PROBE_MIN_DOCS moves the line (the tests put it at 0).
+        bool probe = !knobs().no_probe && cq.simple_n >= 2 && cq.ops[cq.simple_n].kind == OP_AND && uint64_t(idx.doc_hi) - idx.doc_lo >= knobs().probe_min_docs;
+        arr_mask = 0;  // operands probed as 16-bit arrays (2 B per posting) instead of bitmap words (a bit per doc): the fewer bytes win
+        if (probe) {
+            const bool no_arr = knobs().probe_no_arr;
+            uint32_t covers = 0;
+            for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                const HList& l = cq.lists[cq.ops[k].list_begin];
+                if (l.flags & LIST_COVER) {
+                    ++covers;
+                    probe = probe && l.d_cov32;
+                } else {
+                    const bool arr = l.d_arr16 && !no_arr && (!(l.flags & LIST_BITMAP) || uint64_t(l.len) * 16 < uint64_t(idx.doc_hi) - idx.doc_lo);
+                    if (arr) arr_mask |= 1u << k;
+                    probe = probe && (arr || (l.flags & LIST_BITMAP));
+                }
+            }
+            probe = probe && covers == 1;
         }
-        if (!cq.simple_flags) detect_rich_simple();
-        if (!cq.simple_flags) detect_wide();
-        cq.kclass = route_query(cq);  // simple_flags is final: everything below — and the launch (exec.cpp) — goes by the class
+        return probe;
+    }
+    // reads the simple leaves' lists; returns the operand an OR probe streams as its cover (UINT32_MAX: no OR probe) and leaves cq.or_skip_bound
+    uint32_t or_probe_cover() {
+        // An OR of 2 or 3 leaves with a term slot each whose sparsest operand has a tile-packed image and whose other operands are bitmap words, on an
+        // unsharded index: k_scan_probe_or counts the union from the words' set bits and scores only the docs that hold the cover (the
+        // sparsest operand) — a doc without it scores at most `or_skip_bound`, and finish_batch confirms that the request's k-th best key lies
+        // above that before the result is handed out (otherwise the request runs again with exact_routes_only).  Sharded: a rank's partial
+        // leaves for the exchange before the host sees it, so shards keep k_scan_simple.  VQ_NO_PROBE_OR=1 switches the route off.
+        uint32_t or_cover = UINT32_MAX;
+        if (!knobs().no_probe && !knobs().no_probe_or && !req.exact_routes_only && cq.top_k >= 1 && cq.simple_n >= 2 && cq.simple_n <= 3 && cq.ops[cq.simple_n].kind == OP_OR &&
+            cq.ops[cq.simple_n].nslots == cq.simple_n && !idx.sharded() && !(idx.comm && idx.comm->nranks > 1) && uint64_t(idx.doc_hi) - idx.doc_lo >= knobs().probe_min_docs) {
+            for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                const HList& l = cq.lists[cq.ops[k].list_begin];
+                if (l.d_cov32 && (or_cover == UINT32_MAX || l.len < cq.lists[cq.ops[or_cover].list_begin].len)) or_cover = k;
+            }
+            double sum = 0.0, cnt = 0.0;
+            for (uint32_t k = 0; k < cq.simple_n && or_cover != UINT32_MAX; ++k) {
+                if (k == or_cover) continue;
+                const HList& l = cq.lists[cq.ops[k].list_begin];
+                if (!(l.flags & LIST_BITMAP) || (l.flags & LIST_F32) || l.max_raw >= 0x7C00 || !(l.term_score >= 0.0f)) {
+                    or_cover = UINT32_MAX;
+                    break;
+                }
+                const uint16_t h = l.max_raw;  // finite non-negative f16
+                const int e = (h >> 10) & 31, m = h & 1023;
+                const double a = e ? std::ldexp(1.0 + m / 1024.0, e - 15) : std::ldexp(m / 1024.0, -14);
+                const double v = double(l.term_score) * (a / 100.0);
+                if (v >= 0.00001 * (1.0 - 1e-5)) cnt += 1.0;  // (set_op.rs:180: a slot counts from 1e-5 on)
+                sum += v;
+            }
+            if (or_cover != UINT32_MAX) {
+                const HList& c = cq.lists[cq.ops[or_cover].list_begin];
+                if (!(c.term_score > 0.0f) || c.max_raw >= 0x7C00) or_cover = UINT32_MAX;  // (the kernel's bound is taken over the cover's raw scores)
+                else {
+                    const double b = sum * cnt * cnt * (1.0 + 1e-5);  // f32 rounding of the kernel's sums stays below the margin
+                    cq.or_skip_bound = b < 3.0e38 ? float(b) : std::numeric_limits<float>::infinity();
+                    // (never fires — float(b) is the very value assigned above: ADVICE.md; carried over as it is, making it fire moves the bound)
+                    if (cq.or_skip_bound < float(b)) cq.or_skip_bound = std::nextafter(cq.or_skip_bound, std::numeric_limits<float>::infinity());
+                }
+            }
+        }
+        return or_cover;
+    }
+    // reads the simple leaves' lists and the probe decisions; returns the kSf* flag word and leaves cq.probe / cq.probe_arr_gran for the probe and packed-union routes
+    uint32_t simple_flag_word(bool probe, uint32_t arr_mask, uint32_t or_cover) {
+        uint32_t f = kSfSimple;
+        const bool or_probe = or_cover != UINT32_MAX && probe;
+        bool seq = false;
+        for (uint32_t k = 0; k < cq.simple_n && !probe; ++k) {
+            const HList& l = cq.lists[cq.ops[k].list_begin];
+            if ((l.flags & LIST_COVER) && (l.flags & LIST_BITMAP)) seq = true;
+        }
+        if (seq) f |= kSfSeq;
+        if (probe) {
+            f |= kSfProbe | arr_mask << kSfArrayShift | (or_probe ? kSfProbeOr : 0u);
+            cq.probe = DProbe{};
+            for (uint32_t k = 0; k < cq.simple_n; ++k) {
+                const HList& l = cq.lists[cq.ops[k].list_begin];
+                cq.probe.leaf[k] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
+                if ((arr_mask >> k) & 1u) cq.probe_arr_gran = std::max(cq.probe_arr_gran, l.tile_most);
+            }
+        }
+        for (uint32_t k = 0; k < cq.simple_n; ++k) {
+            const HList& l = cq.lists[cq.ops[k].list_begin];
+            const bool cover = or_probe ? k == or_cover : (l.flags & LIST_COVER) != 0;
+            if (cover) f |= 1u << (kSfCoverShift + k);
+            if ((l.flags & LIST_BITMAP) && (seq || !cover) && !((arr_mask >> k) & 1u)) f |= 1u << (kSfBitmapShift + k);
+            if (uint64_t(l.len) * 8192 >= 200 * (uint64_t(idx.doc_hi) - idx.doc_lo)) f |= 1u << (kSfPrefetchShift + k);
+        }
+        // a single leaf whose list has a tile-packed image: k_scan_union streams that (4 B per posting) instead of ids + scores (6 B)
+        if (cq.simple_n == 1 && !knobs().no_union_cov) {
+            const HList& l = cq.lists[cq.ops[0].list_begin];
+            if (l.d_cov32 && l.d_gdir && l.d_tile_dir && l.term_score > 0.0f && !(l.flags & LIST_F32) && l.inline_idx < 0) {
+                f |= kSfUnionPacked;
+                cq.probe = DProbe{};
+                cq.probe.leaf[0] = DProbeLeaf{l.d_cov32, l.d_arr16, l.d_gdir};
+            }
+        }
+        return f;
+    }
+    // reads cq.simple_n and what else the query carries; leaves cq.simple_flags for a pure simple query (k_scan_simple, fixed 8192-doc tiles, or a probe route)
+    void detect_pure_simple() {
+        const bool pure = cq.simple_n && count_reqs.empty() && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
+                          cq.facets.empty() && uint64_t(idx.doc_hi) - idx.doc_lo >= 65536;
+        if (!pure || knobs().force_generic) return;
+        uint32_t arr_mask = 0;
+        bool probe = and_probe_operands(arr_mask);
+        const uint32_t or_cover = probe ? UINT32_MAX : or_probe_cover();
+        probe = probe || or_cover != UINT32_MAX;
+        cq.simple_flags = simple_flag_word(probe, arr_mask, or_cover);
+    }
+    // reads cq.ops, cq.lists and what else the query carries; leaves cq.simple_flags = kSfLeafF32 for one materialised leaf and nothing else
+    void detect_leaf_f32() {
+        // one materialised leaf, nothing else that shapes presence or score: k_scan_leaf_f32 streams the list (facets counted per entry)
+        const bool off = knobs().force_generic || knobs().no_leaf_f32;
+        if (!off && !cq.simple_flags && count_reqs.empty() && cq.ops.size() == 1 && cq.ops[0].kind == OP_LEAF && cq.ops[0].list_count == 1 &&
+            (cq.lists[cq.ops[0].list_begin].flags & LIST_F32) && cq.fops.empty() && cq.groups.empty() && cq.tboosts.empty() && cq.cols.empty() && cq.locf.empty() &&
+            cq.facets.empty())  // (with facets the rich kernel is faster: its 64-hit rounds put less pressure on the histogram's hot counters
+                                //  than every span adding at once — an LDS-privatised histogram would lift that)
+            cq.simple_flags = kSfLeafF32;
+    }
+
+    // reads cq.kclass; leaves the doc set's list without its bitmap image off k_tile_scan, the prune table, cq.seq_tiles and the cover flags that go with it
+    void after_routing() {
         if (docset_list >= 0 && cq.kclass != K_TILE_SCAN) {  // k_tile_scan alone reads an id-only list's bitmap image: the others get the plain id list
             HList& l = cq.lists[size_t(docset_list)];
             l.flags &= ~uint32_t(LIST_BITMAP);
@@ -2391,28 +2132,16 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
                     if (l.flags & LIST_BITMAP) l.flags &= ~uint32_t(LIST_COVER);
             }
         }
+    }
 
+    // reads cq.kclass, cq.lists, cq.total_len, cq.n_temps and the score root's cover length; leaves cq.tile_words, cq.stack_depth, cq.n_spans and cq.max_spans
+    void plan_spans_and_tiles(uint64_t root_cover_len) {
         // ---- tiling: tile width from the LDS budget and the cover density; spans from the work volume
         const uint32_t L = std::max<uint32_t>(uint32_t(cq.lists.size()), 1);
         const uint64_t range = uint64_t(idx.doc_hi) - idx.doc_lo;
-        static const uint32_t ww_max = [] {  // tuning knobs (experiments): VQ_TILE_WORDS_MAX, VQ_TILE_LDS_KB, VQ_SPAN_POSTINGS
-            const char* e = std::getenv("VQ_TILE_WORDS_MAX");
-            uint32_t v = e ? uint32_t(std::atoi(e)) : 256u;
-            uint32_t p2 = 64;
-            while (p2 < v && p2 < 2048) p2 <<= 1;
-            return p2;
-        }();
-        static const size_t var_budget = [] {
-            const char* e = std::getenv("VQ_TILE_LDS_KB");
-            return size_t(e ? std::atoi(e) : 12) * 1024;
-        }();
         // postings per span.  Every span warms its own threshold up (until it adopts the query's shared one), so long spans prune
         // better; short spans fill the chip more evenly.  Measured optimum (100 M docs, 256-query launches): 256 Ki postings, 128 Ki
         // for the rich simple kernel and plain simple ANDs (no threshold-driven pruning to warm up; the tail of the launch weighs more).  VQ_SPAN_POSTINGS overrides.
-        static const uint64_t span_env = [] {
-            const char* e = std::getenv("VQ_SPAN_POSTINGS");
-            return uint64_t(e ? std::atoll(e) : 0);
-        }();
         // (on a small shard the same number of spans per query is kept — a 1/8 shard with 1 Mi-posting spans would leave half the chip without a wave)
         const uint64_t probe_span = std::min<uint64_t>(std::max<uint64_t>(range / 96, 131072), 1048576);
         uint64_t span_postings = 262144;
@@ -2428,12 +2157,13 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
             case K_SCAN_SIMPLE: span_postings = (cq.simple_n > 1 && range >= 50'000'000ull) ? 524288 : 262144; break;
             default: break;
         }
-        if (span_env) span_postings = span_env;
-        uint32_t ww = ww_max;  // W = 32 * ww docs
+        if (knobs().span_postings) span_postings = knobs().span_postings;
+        uint32_t ww = knobs().tile_words_max;  // W = 32 * ww docs
+        const size_t var_budget = knobs().tile_lds_bytes;
         const size_t TL = size_t(L) + cq.n_temps;
         while (ww > 64 && (size_t(ww) + TL * ww + size_t(L) * ww / 2) * 4 > var_budget) ww >>= 1;
         if ((size_t(ww) + TL * ww + size_t(L) * ww / 2) * 4 > 96 * 1024) unsupported("too many lists for the LDS tile");
-        const uint64_t cover_len = std::max<uint64_t>(root.cover_len, 1);
+        const uint64_t cover_len = std::max<uint64_t>(root_cover_len, 1);
         // a sparse cover visits about one tile per cover doc: shrink the tile until it holds ~1 cover entry,
         // so that the per-tile clear / prefix work stays proportional to what is actually read
         if (cover_len * (uint64_t(ww) << 5) / std::max<uint64_t>(range, 1) < 64) {
@@ -2444,10 +2174,7 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         cq.tile_words = ww;
         cq.stack_depth = std::max<uint32_t>(max_depth, 1);
         uint64_t spans = (cq.total_len + span_postings - 1) / span_postings;
-        static const uint64_t facet_span = [] {
-            const char* e = std::getenv("VQ_FACET_SPAN_POSTINGS");
-            return uint64_t(e ? std::atoll(e) : 4096);
-        }();
+        const uint64_t facet_span = knobs().facet_span_postings;
         if (!cq.facets.empty()) spans = (cq.total_len + facet_span - 1) / facet_span;  // every hit walks its facet rows: per-hit work, not per-posting streaming
         const uint64_t tiles = std::max<uint64_t>((range + (uint64_t(ww) << 5) - 1) / (uint64_t(ww) << 5), 1);
         {  // k_tile_scan pays a latency-bound round trip per visited tile (score gathers, facet rows): at most ~16 visited tiles per span
@@ -2468,6 +2195,44 @@ struct Compiler : CompileInputs {  // (fuzzy, unions, counts, ranges, boost_cach
         }
         cq.max_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(tiles, 1), 4096));
         if (cq.kclass == K_SCAN_LEAF_F32) cq.max_spans = uint32_t(std::min<uint64_t>(std::max<uint64_t>(cq.lists[cq.ops[0].list_begin].len / 64, 1), 4096));
+    }
+
+    // ------------------------------------------------------------ the whole request (search.rs:143-228)
+    void run() {
+        cq.lists.reserve(8);  // (the vectors of a typical request: one allocation each instead of a growth chain)
+        cq.ops.reserve(8);
+        cq.pres.reserve(8);
+        cq.pres_in.reserve(16);
+        by_address.reserve(8);
+        if (req.filter_only) return run_filter_only();
+        // (`select` itself is not looked at: search::search leaves the reading of the selected fields to to_documents, search.rs:63-103; together with
+        //  why_found it asks for why_found_info, :220-224 — complete_why_found_requests)
+        // (`suggest` is not looked at either: search::search reads search_req, search.rs:151-155; suggest_multi is vq_suggest_json)
+        if (!req.search_req) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"search_req is None, but is required in search\" ");
+        plan_page();
+        collect_leaves();
+        decide_explain();
+        const NodeInfo root = compile_trees();
+        add_column_boosts();
+        finish_explain_plan(root);
+        append_leaf_cols();
+        add_phrase_boosts();
+        add_term_boosts();
+        plan_why_found();
+        add_text_locality();
+        add_facets();
+        settle_count_requests();
+        build_presence_program();
+        if (!count_reqs.empty())  // count pre-pass: every tile that holds a doc of any list is visited
+            for (auto& l : cq.lists) l.flags |= LIST_COVER;
+        detect_simple();
+        detect_pure_simple();  // the routes, in their order of precedence: the first that takes the query sets cq.simple_flags
+        detect_leaf_f32();
+        if (!cq.simple_flags) detect_rich_simple();
+        if (!cq.simple_flags) detect_wide();
+        cq.kclass = route_query(cq);  // simple_flags is final: everything below — and the launch (exec.cpp) — goes by the class
+        after_routing();
+        plan_spans_and_tiles(root.cover_len);
         compute_layout_bytes(root.cover_len);
     }
 
@@ -2585,434 +2350,11 @@ KernelId route_query(const CompiledQuery& cq) {
     return K_SCAN_SIMPLE;
 }
 
-float default_score_for_distance_host(uint8_t distance, bool prefix_matches) { return default_score_for_distance(distance, prefix_matches); }
 size_t debug_sort_unique(uint32_t* ids, size_t n) {  // (tests: the three regimes of sort_unique_u32 against an independent sort)
     std::vector<uint32_t> v(ids, ids + n);
     sort_unique_u32(v);
     std::copy(v.begin(), v.end(), ids);
     return v.size();
-}
-
-// suggest (search_field.rs:194-219): one part's matched terms with lower-cased texts and scores — get_term_ids_in_field with get_scores,
-// return_term and return_term_lowercase; the dictionary scan of a fuzzy / prefix part has run on the device (`fuzzy`).
-std::vector<SuggestEntry> suggest_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy, bool topn_probes) {
-    Request dummy;
-    CompileInputs in{fuzzy};
-    in.topn_probes = topn_probes;
-    Compiler c(idx, dummy, in);
-    Leaf l;
-    l.part = &part;
-    l.get_scores = true;
-    l.return_term = true;
-    l.return_term_lowercase = true;
-    c.lookup_terms(idx, l, true, false);
-    if (part.token_value) c.apply_token_value(*part.token_value, l);
-    std::vector<SuggestEntry> out;
-    std::map<uint32_t, const std::string*> text;
-    for (auto& t : l.terms) text[t.first] = &t.second;
-    for (auto& h : l.hits_scores) out.push_back(SuggestEntry{*text.at(h.first), h.second, h.first});
-    return out;
-}
-
-
-// highlight (search_field.rs:233-245): the texts that contain a matched token, each with its snippet (highlight_field.rs:187-272) and the
-// best score among its matched tokens (resolve_token_hits_to_text_id with snippets, search_field.rs:550-639).  `part.terms` are already
-// normalised; the dictionary scan of a fuzzy / prefix part has run on the device (`fuzzy`).  Host work over the host copies of
-// tokens_to_text_id / text_id_to_token_ids: one text at a time, a few dozen tokens each.
-namespace {
-// the snippet of n tokens: is_hit(i) marks the tokens to tag, append(out, i) writes token i's text
-template <class IsHit, class Append>
-std::string snippet_of_tokens(size_t n, IsHit is_hit, Append append_text, const vqreq::SnippetInfo& opt, bool* any) {
-    const int64_t around = opt.num_words_around_snippet * 2;  // token separator token separator
-    // one walk: hits closer than `around` tokens share a window (group_hit_positions_for_snippet :19-37); a window reaches `around` tokens
-    // to both sides of its hits (grouped_to_positions_for_snippet :39-43)
-    std::string out;
-    int64_t first_hit = -1, last_hit = -1, group_first = -1, group_last = -1;
-    uint64_t windows = 0;
-    auto close_group = [&]() {
-        if (group_first < 0) return;
-        if (windows < opt.max_snippets) {
-            if (windows) out += opt.snippet_connector;
-            const size_t lo = size_t(std::max<int64_t>(group_first - around, 0)), hi = size_t(std::min<int64_t>(group_last + around + 1, int64_t(n)));
-            for (size_t i = lo; i < hi; ++i) {
-                if (is_hit(i)) {
-                    out += opt.snippet_start_tag;
-                    append_text(out, i);
-                    out += opt.snippet_end_tag;
-                } else append_text(out, i);
-            }
-        }
-        ++windows;
-    };
-    for (size_t i = 0; i < n; ++i) {
-        if (!is_hit(i)) continue;
-        if (first_hit < 0) first_hit = int64_t(i);
-        if (group_first < 0 || int64_t(i) - group_last >= around) {
-            close_group();
-            group_first = int64_t(i);
-        }
-        group_last = last_hit = int64_t(i);
-    }
-    close_group();
-    *any = first_hit >= 0;
-    if (!*any) return out;
-    if (first_hit > around) out.insert(0, opt.snippet_connector);             // ellipsis_snippet :73-90
-    if (last_hit < int64_t(n) - around) out += opt.snippet_connector;
-    return out;
-}
-std::string snippet_of_text(const Dictionary& dict, const uint32_t* toks, size_t n, const std::vector<uint32_t>& wanted_sorted, const vqreq::SnippetInfo& opt, bool* any) {
-    return snippet_of_tokens(
-        n, [&](size_t i) { return std::binary_search(wanted_sorted.begin(), wanted_sorted.end(), toks[i]); },
-        [&](std::string& out, size_t i) {
-            if (toks[i] < dict.terms.size()) out += dict.terms[toks[i]];
-        },
-        opt, any);
-}
-void check_snippet_window(const vqreq::SnippetInfo& opt) {
-    if (opt.num_words_around_snippet < 0 || opt.num_words_around_snippet > 0x3FFFFFFF)  // the reference's window arithmetic overflows / panics there
-        throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"snippet_info.num_words_around_snippet out of range\" ");
-}
-}  // namespace
-
-// highlight_text (highlight_field.rs:92-146): `text` with the tokens that are in `terms` tagged — what why_found highlighting applies to every text
-// of a returned document (highlight_on_original_document, :148-185) with the field's why_found_terms.  nullopt: nothing to highlight.
-std::optional<std::string> highlight_text(const std::string& text, const std::vector<std::string>& terms, const vqreq::SnippetInfo& opt, bool tokenized) {
-    check_snippet_window(opt);
-    std::vector<std::string> set = terms;
-    std::sort(set.begin(), set.end());
-    set.erase(std::unique(set.begin(), set.end()), set.end());
-    if (set.size() == 1 && set[0] == text) return opt.snippet_start_tag + text + opt.snippet_end_tag;  // one hit that is the whole text
-    if (!tokenized) return std::nullopt;
-    const std::vector<vqtext::TokenSpan> tokens = vqtext::tokenize_grouped(text);
-    std::vector<char> hit(tokens.size(), 0);
-    for (size_t i = 0; i < tokens.size(); ++i) hit[i] = std::binary_search(set.begin(), set.end(), text.substr(tokens[i].begin, tokens[i].end - tokens[i].begin));
-    bool any = false;
-    std::string out = snippet_of_tokens(
-        tokens.size(), [&](size_t i) { return hit[i] != 0; }, [&](std::string& o, size_t i) { o.append(text, tokens[i].begin, tokens[i].end - tokens[i].begin); }, opt, &any);
-    // (contains_any_token is set while the windows are written: with max_snippets == 0 nothing is)
-    if (!any || opt.max_snippets == 0) return std::nullopt;
-    return out;
-}
-
-static const vqreq::SnippetInfo kDefaultSnippetInfo;
-HighlightLookup highlight_lookup(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
-    check_snippet_window(part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo);
-    RequestSearchPart lookup = part;  // get_term_ids_in_field does not look at the snippet fields
-    lookup.snippet.reset();
-    lookup.has_snippet_info = false;
-    Request dummy;
-    Compiler c(idx, dummy, CompileInputs{fuzzy});
-    Leaf l;
-    l.part = &lookup;
-    l.get_scores = true;
-    c.lookup_terms(idx, l, true, false);
-    if (lookup.token_value) c.apply_token_value(*lookup.token_value, l);
-    HighlightLookup lk;
-    lk.path = l.path;
-    lk.hits_scores = std::move(l.hits_scores);
-    auto cit = idx.columns.find(lk.path.substr(0, lk.path.size() - std::strlen(TEXTINDEX)));
-    lk.tokenized = cit != idx.columns.end() && cit->second.tokenize;
-    lk.add_snippets = part.snippet.value_or(false);
-    return lk;
-}
-
-bool highlight_snippet(const Index& idx, const HighlightLookup& lk, const RequestSearchPart& part, uint32_t text, const std::vector<uint32_t>& wanted_sorted, std::string* out) {
-    const vqreq::SnippetInfo& opt = part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo;
-    auto tit = idx.kv.find(lk.path + ".text_id_to_token_ids");
-    if (tit == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + lk.path + ".text_id_to_token_ids");
-    const uint32_t *b, *e;
-    if (!tit->second.host_row(text, &b, &e)) return false;
-    bool any = false;
-    *out = snippet_of_text(idx.dict.at(lk.path), b, size_t(e - b), wanted_sorted, opt, &any);
-    return any;
-}
-
-std::vector<SuggestEntry> highlight_part(const Index& idx, const RequestSearchPart& part, const FuzzyTable* fuzzy) {
-    return highlight_resolve(idx, part, highlight_lookup(idx, part, fuzzy));
-}
-
-std::vector<SuggestEntry> highlight_resolve(const Index& idx, const RequestSearchPart& part, const HighlightLookup& l) {
-    const vqreq::SnippetInfo& opt = part.has_snippet_info ? part.snippet_info : kDefaultSnippetInfo;
-    struct TextHit {
-        uint32_t text;
-        float score;
-        uint32_t token, order;
-    };
-    std::vector<TextHit> hits;
-    std::vector<std::pair<uint32_t, float>> ranked;  // (text id, best score): SearchFieldResult::hits_scores after the resolve step
-    const std::string& path = l.path;
-    const bool tokenized = l.tokenized;
-    const bool add_snippets = l.add_snippets;
-    std::map<uint32_t, std::string> snippets;
-    for (auto& h : l.hits_scores) ranked.push_back(h);
-    if (tokenized) {
-        auto kit = idx.kv.find(path + TOKENS_TO_TEXT_ID);
-        if (kit == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path + TOKENS_TO_TEXT_ID);
-        uint32_t order = 0;
-        for (auto& h : l.hits_scores) {
-            const uint32_t *b, *e;
-            if (!kit->second.host_row(h.first, &b, &e)) continue;
-            for (const uint32_t* v = b; v != e; ++v) hits.push_back({*v, h.second, h.first, order++});
-        }
-        std::sort(hits.begin(), hits.end(), [](const TextHit& a, const TextHit& b) { return a.text != b.text ? a.text < b.text : a.order < b.order; });
-        if (!hits.empty()) {
-            if (add_snippets) ranked.clear();  // :608-610
-            const KVStore* t2t = nullptr;
-            const Dictionary& dict = idx.dict.at(path);
-            std::vector<uint32_t> wanted;
-            for (size_t i = 0; i < hits.size();) {
-                size_t j = i;
-                float best = hits[i].score;
-                wanted.clear();
-                for (; j < hits.size() && hits[j].text == hits[i].text; ++j) {
-                    if (std::fabs(hits[j].score) >= std::fabs(best)) best = hits[j].score;  // Iterator::max_by_key keeps the last maximum
-                    wanted.push_back(hits[j].token);
-                }
-                const uint32_t text = hits[i].text;
-                ranked.push_back({text, best});
-                if (add_snippets) {
-                    if (!t2t) {
-                        auto tit = idx.kv.find(path + ".text_id_to_token_ids");
-                        if (tit == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + path + ".text_id_to_token_ids");
-                        t2t = &tit->second;
-                    }
-                    std::sort(wanted.begin(), wanted.end());
-                    const uint32_t *b, *e;
-                    if (t2t->host_row(text, &b, &e)) {
-                        bool any = false;
-                        std::string sn = snippet_of_text(dict, b, size_t(e - b), wanted, opt, &any);
-                        if (any) snippets[text] = std::move(sn);
-                    } else if (std::binary_search(wanted.begin(), wanted.end(), text))  // the text is its own only token: all of it (highlight_field.rs:198-203)
-                        snippets[text] = opt.snippet_start_tag + (text < dict.terms.size() ? dict.terms[text] : std::string()) + opt.snippet_end_tag;
-                }
-                i = j;
-            }
-        }
-    }
-    std::vector<SuggestEntry> out;
-    for (auto& r : ranked) {  // get_text_score_id_from_result(false, ..) search_field.rs:160-192: indexing `highlight` panics for a hit without a snippet
-        auto it = snippets.find(r.first);
-        if (it == snippets.end())
-            throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"highlight: hit " + std::to_string(r.first) + " has no snippet (the reference panics)\" ");
-        out.push_back(SuggestEntry{it->second, r.second, r.first});
-    }
-    return out;
-}
-
-// get_why_found (src/search/why_found.rs:11-50) for the finished requests that asked for why_found together with select: for every searched field
-// and every returned anchor, the anchor's texts of the field (join_anchor_to_leaf, facet.rs:75-93) highlighted with all term ids the search matched
-// there (highlight_document with DEFAULT_SNIPPETINFO, highlight_field.rs:187-272); a text without a hit leaves no entry.
-void complete_why_found_requests(const Index& idx, std::vector<std::unique_ptr<Result>>& results, std::vector<int>& status, std::vector<std::string>& errors) {
-    static const vqreq::SnippetInfo kDefault;
-    for (size_t i = 0; i < results.size(); ++i) {
-        if (status[i] != 0 || !results[i] || !results[i]->why_found_plan) continue;
-        Result& R = *results[i];
-        try {
-            for (auto& [path, wanted] : *R.why_found_plan) {  // (wanted: sorted, unique)
-                if (wanted.empty() || R.ids.empty()) continue;  // why_found.rs:29-31
-                const std::string field_name = path.substr(0, path.size() - std::strlen(TEXTINDEX));
-                const std::vector<std::string> steps = get_steps_to_anchor(field_name);
-                auto store = [&](const std::string& name) -> const KVStore& {
-                    auto it = idx.kv.find(name);
-                    if (it == idx.kv.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + name);
-                    return it->second;
-                };
-                std::vector<const KVStore*> chain;
-                for (auto& st : steps) chain.push_back(&store(st + PARENT_TO_VALUE_ID));
-                const KVStore& t2t = store(steps.back() + ".text_id_to_token_ids");
-                auto dit = idx.dict.find(steps.back());
-                if (dit == idx.dict.end()) throw VelociError(ERR_INDEX_NOT_FOUND, "Did not found path in indices " + steps.back() + ".fst");
-                const Dictionary& dict = dit->second;
-                std::vector<uint32_t> level, next;
-                for (uint32_t anchor : R.ids) {
-                    level.assign(1, anchor);
-                    for (const KVStore* st : chain) {
-                        next.clear();
-                        for (uint32_t id : level) {
-                            const uint32_t *rb, *re;
-                            if (st->host_row(id, &rb, &re)) next.insert(next.end(), rb, re);
-                        }
-                        level.swap(next);
-                    }
-                    for (uint32_t value_id : level) {
-                        const uint32_t *b, *e;
-                        if (t2t.host_row(value_id, &b, &e)) {
-                            bool any = false;
-                            std::string sn = snippet_of_text(dict, b, size_t(e - b), wanted, kDefault, &any);
-                            if (any) R.why_found_info[anchor][field_name].push_back(std::move(sn));
-                        } else if (std::binary_search(wanted.begin(), wanted.end(), value_id))  // the text is its own only token: all of it (highlight_field.rs:198-203)
-                            R.why_found_info[anchor][field_name].push_back(kDefault.snippet_start_tag + (value_id < dict.terms.size() ? dict.terms[value_id] : std::string()) +
-                                                                           kDefault.snippet_end_tag);
-                    }
-                }
-            }
-        } catch (const VelociError& e) {
-            status[i] = e.code;
-            errors[i] = e.what();
-            results[i].reset();
-        }
-    }
-}
-
-// ---- dictionary scans requested by a batch (collected before compilation, answered by k_dict_scan)
-std::string fuzzy_key(const RequestSearchPart& p) {
-    std::string path = p.path;
-    if (!ends_with(path, TEXTINDEX)) path += TEXTINDEX;
-    std::string k;
-    key_s(k, path);
-    key_s(k, p.terms.empty() ? std::string() : p.terms[0]);
-    k += std::to_string(clamped_lev(p)) + (p.starts_with ? "p" : "-") + (p.ignore_case ? (*p.ignore_case ? "T" : "F") : "N");
-    if (p.is_regex) k += 'R';
-    return k;
-}
-bool needs_dictionary_scan(const RequestSearchPart& p) { return !p.terms.empty() && !p.is_regex && (clamped_lev(p) != 0 || p.starts_with); }
-std::string topn_key(const RequestSearchPart& p) { return fuzzy_key(p) + "#" + std::to_string(p.top.value_or(10)) + "+" + std::to_string(p.skip.value_or(0)); }
-
-// VQ_NO_SUGGEST_TOPN=1: every part of a suggest batch keeps the full route (all matches back, the top-n loop on the host)
-static bool suggest_topn_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("VQ_NO_SUGGEST_TOPN");
-        return !(e && *e && std::string(e) != "0");
-    }();
-    return on;
-}
-// what run_fuzzy_probes decides per probe: k_dict_scan takes a 16-bit image and a query of <= 64 code points below U+10000, every other probe
-// goes to k_dict_scan_wide; either scores a hit itself when the lower-cased term has at most 64 code points (k_dict_scan: all below U+10000)
-// and the lower-cased image is exact
-bool probe_scored_on_device(const Index& idx, const FuzzyProbe& fp) {
-    const Dictionary& d = idx.dict.at(fp.path);
-    bool wide = d.char_bytes != 2 || fp.query.size() > 64;
-    for (uint32_t cp : fp.query) wide = wide || cp > 0xFFFFu;
-    const auto lcps = vqtext::decode_utf8(fp.lower_term);
-    bool ok = lcps.size() <= 64 && d.low_exact;
-    if (!wide)
-        for (uint32_t cp : lcps) ok = ok && cp <= 0xFFFFu;
-    return ok;
-}
-
-// VQ_NO_REGEX_DEVICE=1: every regex leaf stays on the host route
-static bool regex_device_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("VQ_NO_REGEX_DEVICE");
-        return !(e && *e && std::string(e) != "0");
-    }();
-    return on;
-}
-vqregex::Compiled regex_route(const Index& idx, const RequestSearchPart& p) {
-    if (!p.is_regex) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "not a regex part (is_regex is false)");
-    if (p.terms.empty()) throw VelociError(ERR_INVALID_REQUEST, "InvalidRequest: \"terms is empty\" ");
-    std::string path = p.path;
-    if (!ends_with(path, TEXTINDEX)) path += TEXTINDEX;
-    auto dit = idx.dict.find(path);
-    if (dit == idx.dict.end()) throw VelociError(ERR_FST_NOT_FOUND, "field does not exist " + path + " (fst not found)");
-    {  // first, always: an invalid pattern is the host route's error, word for word
-        std::wregex whole, anywhere;
-        regex_objects(p, whole, anywhere);
-    }
-    if (!regex_device_enabled()) {
-        vqregex::Compiled c;
-        c.reason = "VQ_NO_REGEX_DEVICE is set";
-        return c;
-    }
-    const Dictionary& d = dit->second;
-    return vqregex::compile(vqtext::decode_utf8(p.terms[0]), p.ignore_case.value_or(true), p.starts_with, d.alphabet, *d.regex_atoms);
-}
-static void probe_regex_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table) {
-    if (!regex_device_enabled() || p.terms.empty()) return;
-    const std::string key = fuzzy_key(p);
-    if (table.count(key)) return;
-    vqregex::Compiled c;
-    try {
-        c = regex_route(idx, p);
-    } catch (const VelociError&) {
-        return;  // the compiler reports it, request by request
-    }
-    if (!c.device) return;  // host route (Compiler::regex_candidates)
-    FuzzyProbe fp;
-    fp.key = key;
-    fp.path = p.path;
-    if (!ends_with(fp.path, TEXTINDEX)) fp.path += TEXTINDEX;
-    fp.regex = true;
-    fp.dfa = std::move(c.dfa);
-    table.emplace(key, std::move(fp));
-}
-
-// suggest_batch: a part with its own top whose top + skip fits k_dict_topn's buffer asks for a top-n probe (key: topn_key) when the device scores
-// its hits and neither distance can reach the u8 cap (lower-cased term below 255 bytes, every term of the dictionary below 200: then the
-// long-string branch of the scoring rule cannot occur either)
-static void probe_part(const Index& idx, const RequestSearchPart& p, FuzzyTable& table, bool suggest_batch = false) {
-    if (p.is_regex) return probe_regex_part(idx, p, table);
-    if (!needs_dictionary_scan(p)) return;
-    const std::string key = fuzzy_key(p);
-    const size_t top_n = p.top.value_or(0) + p.skip.value_or(0);
-    const bool ask_topn = suggest_batch && suggest_topn_enabled() && p.top && top_n >= *p.top && top_n >= 1 && top_n <= kTopnMax;
-    if (table.count(ask_topn ? topn_key(p) : key)) return;
-    FuzzyProbe fp;
-    fp.key = key;
-    fp.path = p.path;
-    if (!ends_with(fp.path, TEXTINDEX)) fp.path += TEXTINDEX;
-    auto dit = idx.dict.find(fp.path);
-    if (dit == idx.dict.end()) return;  // the compiler reports FstNotFound
-    // match-set automaton (search_field.rs:85-95): built from the ORIGINAL term
-    fp.max_d = std::min<uint32_t>(clamped_lev(p), 4);
-    fp.transposition = p.ignore_case.value_or(false);
-    fp.ci = p.ignore_case.value_or(true);
-    fp.prefix = p.starts_with;
-    fp.lower_term = vqtext::to_lower_utf8(p.terms[0]);
-    fp.lev = clamped_lev(p);
-    fp.check_prefix = p.starts_with || fp.lev != 0;  // :302
-    const auto cps = vqtext::decode_utf8(p.terms[0]);
-    if (cps.size() >= kDictMaxPattern) {
-        fp.status = ERR_UNSUPPORTED;
-        fp.error = "fuzzy / prefix search with a term of " + std::to_string(cps.size()) + " characters (the dictionary scan takes fewer than " +
-                   std::to_string(kDictMaxPattern) + ")";
-    }
-    for (uint32_t cp : cps) fp.query.push_back(fp.ci ? vqtext::lower_cp(cp) : cp);
-    if (ask_topn && fp.status == 0 && fp.lower_term.size() < 255 && dit->second.max_term_bytes < 200 && probe_scored_on_device(idx, fp)) {
-        fp.top_n = uint32_t(top_n);
-        fp.key = topn_key(p);
-        table.emplace(fp.key, std::move(fp));
-        return;
-    }
-    if (!table.count(key)) table.emplace(key, std::move(fp));
-}
-static void probe_tree(const Index& idx, const SearchRequest& r, FuzzyTable& table) {
-    if (r.kind == SearchRequest::Search) probe_part(idx, r.part, table);
-    else
-        for (auto& q : r.tree.queries) probe_tree(idx, q, table);
-}
-// score of every match of a probe (search_field.rs:304-321), shared by all requests of the batch that contain the leaf
-void score_fuzzy_probe(const Index& idx, FuzzyProbe& fp) {
-    if (fp.status != 0) return;
-    const Dictionary& dict = idx.dict.at(fp.path);
-    fp.scores.resize(fp.matches.size());
-    for (size_t i = 0; i < fp.matches.size(); ++i) {
-        const std::string lower_hit = vqtext::to_lower_utf8(dict.terms[fp.matches[i]]);
-        const bool prefix_matches = fp.check_prefix && lower_hit.size() >= fp.lower_term.size() && lower_hit.compare(0, fp.lower_term.size(), fp.lower_term) == 0;
-        fp.scores[i] = default_score_for_distance(scoring_distance(lower_hit, fp.lower_term, fp.lev), prefix_matches);
-    }
-}
-
-void collect_suggest_probes(const Index& idx, const Request& req, FuzzyTable& table) {
-    if (req.suggest)
-        for (auto& p : *req.suggest) probe_part(idx, p, table);
-}
-
-void collect_suggest_batch_probes(const Index& idx, const Request& req, FuzzyTable& table) {
-    if (req.suggest)
-        for (auto& p : *req.suggest) probe_part(idx, p, table, true);
-}
-
-void collect_fuzzy_probes(const Index& idx, const Request& req, FuzzyTable& table) {
-    if (req.search_req) probe_tree(idx, *req.search_req, table);
-    if (req.filter) probe_tree(idx, *req.filter, table);
-    if (req.phrase_boosts)
-        for (auto& pb : *req.phrase_boosts) {
-            probe_part(idx, pb.search1, table);
-            probe_part(idx, pb.search2, table);
-        }
-    if (req.boost_term)
-        for (auto& p : *req.boost_term) probe_part(idx, p, table);
 }
 
 // request.explain goes into the options of every part before the parts are collected — it is part of their equality (execution_plan.rs:46-106)

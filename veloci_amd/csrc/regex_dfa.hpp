@@ -4,7 +4,7 @@
 // characters an atom (a literal, `.`, a bracket expression, `\d \D \w \W \s \S`) matches is asked of std::wregex itself, atom by atom and code
 // point by code point of the dictionary's alphabet, with the flags of the leaf: icase, `.`, ranges and the C locale's classes are libstdc++'s
 // own answers, not restated here.  Everything outside that structure is declined with a reason and stays on the host route
-// (Compiler::regex_candidates), which is also the yardstick: same match set, same errors.
+// (regex_candidates, term_lookup.cpp), which is also the yardstick: same match set, same errors.
 //
 // Stand-alone on purpose (no HIP, no engine headers): tests/native/regex_dfa_check.cpp links it alone, under the sanitizers.
 #pragma once

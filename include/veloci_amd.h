@@ -146,6 +146,8 @@ uint64_t vq_index_device_bytes(const vq_index*);
 typedef struct vq_request vq_request;
 
 int vq_request_parse(const char* json, size_t len, vq_request** out);
+/* A handle given to vq_search_batch_partial(_at) or vq_shard_step_begin may be freed as soon as the call returns, while the partial batch or
+ * step is still alive: they share the parsed request with the handle.  Every other entry point is done with its requests when it returns. */
 void vq_request_free(vq_request*);
 /* What the parser understood: every field of search::Request (src/search/request/mod.rs:15-87, search_request.rs:6-179, boost_request.rs:4-33,
  * facet_request.rs:2-11) in declaration order, absent Options as null, `select` / `snippet_info` as "present" booleans, f32 values as their bit
@@ -241,7 +243,8 @@ uint64_t vq_debug_docset_part(const vq_docset*, int part, uint32_t* out, uint64_
  * the filter's program), counting and scanning, expanding; 0, or -1 when the set recorded none */
 int vq_debug_docset_timings(const vq_docset*, float* ms_mark, float* ms_count_scan, float* ms_expand);
 void vq_docset_free(vq_docset*);
-/* attaches the set to the request (NULL detaches).  The request keeps the set alive: freeing the handle afterwards is allowed. */
+/* attaches the set to the request (NULL detaches).  The request keeps the set alive: freeing the handle afterwards is allowed.  A partial batch
+ * or step in flight that was made from the request is not affected: it keeps the set the request had when the batch was made. */
 int vq_request_set_docset(vq_request*, const vq_docset*);
 
 /* ---------------------------------------------------------------- results
@@ -378,6 +381,9 @@ int vq_search_batch_flat(const vq_index*, const vq_request* const* requests, siz
  * the caller (RCCL all-gather of the packed buffers). */
 typedef struct vq_partial_batch vq_partial_batch;
 
+/* The batch keeps the requests it was made from alive (a merge may run one again): the handles in `requests` may be freed, or given another
+ * doc set (vq_request_set_docset: the batch keeps the set it was made with), as soon as the call returns.  The same holds for
+ * vq_search_batch_partial_at. */
 int vq_search_batch_partial(const vq_index*, const vq_request* const* requests, size_t n,
                             vq_partial_batch** out);
 /* Packed, fixed-size representation of the partials (same size on every shard
@@ -431,7 +437,9 @@ void vq_partial_free(vq_partial_batch*);
  * pipeline without an exchange: begin / end then keep two batches in flight on an unsharded index.
  * `vq_comm_init_custom` takes the exchange from the caller instead (all-gather of `bytes_per_rank` bytes per rank into a rank-major
  * buffer; in-place sum of u32 counters — both on device memory, to be ordered on `hip_stream` or finished before they return): several
- * shards inside one process, tests. */
+ * shards inside one process, tests.
+ * The handles passed to `vq_shard_step_begin` may be freed, or given another doc set, as soon as the call returns: the step keeps the requests,
+ * and the doc sets, it was begun with until it is ended or freed. */
 #define VQ_COMM_ID_BYTES 128
 typedef struct vq_shard_step vq_shard_step;
 typedef int (*vq_allgather_fn)(void* ctx, const void* local_device, void* gathered_device, size_t bytes_per_rank, void* hip_stream);

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE — the vq_debug_*_lists entry points (capi.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, as a program of its own
+// TEST INFRASTRUCTURE — the vq_debug_*_lists entry points (capi_debug.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, as a program of its own
 // (run by tests/test_prepass_debug_cpu.py): built with g++ -fsanitize=address,undefined from the library's host sources and the stubbed device
 // layer (hip_stub*.cpp).  With VQ_STUB_NOOP_LAUNCH=1, which this program sets, the launchers return without doing anything and "device" memory is
 // zeroed host memory: every driver runs to its end over empty results, so the job tables, the drivers' host side and the copy of every list with

@@ -229,7 +229,7 @@ def test_in_library_step_with_two_gloo_ranks(scenario):
     """vq_shard_step_begin / _end driven from TWO processes through vq_comm_init_custom (the exchange: gloo), on the host-stub build of the
     library — pipelined steps with and without facet histograms issue the same collectives in the same order on both ranks (`ok`); when one
     rank's step fails between its collectives, BOTH ranks get an error for that step instead of one of them waiting for ever, the communicator
-    is down afterwards on both, and the shard answers alone again once it is destroyed (`fail`).  SURVEY.md 8(e); capi.cpp vq_shard_step_*."""
+    is down afterwards on both, and the shard answers alone again once it is destroyed (`fail`).  SURVEY.md 8(e); shard_step.cpp vq_shard_step_*."""
     outs = _run_gloo_step_drivers(scenario)
     for rank, (rc, o, e) in enumerate(outs):
         assert rc == 0 and "GLOO_STEP_DRIVER_OK" in o, f"rank {rank} rc {rc}\n{o[-1500:]}\n{e[-4000:]}"

@@ -1138,6 +1138,49 @@ def test_probe_or_kernel_shapes_and_reruns(corpus, big_corpus):
             assert plain_reruns == 0, plain_reruns  # (the planted overlap puts the best hits into all three lists)
 
 
+def test_step_outlives_its_request_handles(corpus):
+    """A step keeps the requests it was begun with (PartialBatch::owners): two steps begun from RequestBatches that are dropped at once — their
+    handles freed, the memory taken by a few hundred other requests — and ended afterwards.  Among the requests the ones a step reads again at
+    its end: deep ones (paged on by vq_shard_step_end) and ORs whose short cut is refused (run again on the exact kernels by finish_batch).
+    Every output equals vq_search_batch_flat of the same requests, held alive, bit for bit."""
+    import gc
+    import veloci_amd
+    from veloci_amd import dist, synth
+    data, meta, _, _ = corpus
+    idx = veloci_amd.Index(data, device=0)  # (an index of its own: the step leaves a local communicator behind)
+    a, b = list(meta.triples[0]), list(meta.triples[1])
+    leaf = lambda t, boost=None: {"search": dict({"path": "body", "terms": [t]}, **({"boost": boost} if boost is not None else {}))}
+    orq = lambda leaves, **kw: dict({"search_req": {"or": {"queries": leaves}}, "top": 10}, **kw)
+    reqs = [dict(synth.req_or(a, top=5), skip=2000), synth.req_or(a, top=1500)]
+    reqs += [orq([leaf(a[0], 5.0), leaf(a[1], 4.0), leaf(a[2], 0.001)]), orq([leaf(a[0]), leaf(a[1]), leaf(a[2], 0.0)]), orq([leaf(a[0], 9.0), leaf(a[2], 0.01)], top=50),
+             orq([leaf(a[0]), leaf(a[1], -1.0), leaf(a[2])]), orq([leaf(a[0]), leaf(a[1]), leaf(a[2], -2.0)])]
+    reqs += [synth.req_and(a), synth.req_and(b), synth.req_and([a[0], b[1]], top=30)]
+    stride = 1500
+    held = veloci_amd.RequestBatch(reqs)
+    want = veloci_amd.search_batch_flat(held, idx, stride=stride)
+    assert not want[4].any() and int(want[1][1]) == min(1500, int(want[0][1])), (want[4], want[0], want[1])  # (every request answered, the deep window whole)
+    others = [dict(synth.req_and([b[i % 3], a[(i + 1) % 3]], top=3 + i % 40), skip=i) for i in range(300)]
+
+    def begin():
+        return dist.shard_step_begin(idx, veloci_amd.RequestBatch(reqs))  # the batch, and with it every handle, goes when this returns
+
+    before = idx.speculative_reruns
+    s1 = begin()
+    gc.collect()
+    reuse = [veloci_amd.Request(r) for r in others]
+    s2 = begin()
+    gc.collect()
+    reuse += [veloci_amd.Request(r) for r in others]
+    got = [dist.shard_step_end(s1, stride), dist.shard_step_end(s2, stride)]
+    reran = idx.speculative_reruns - before
+    del reuse
+    for g in got:
+        for name, x, w in zip(("num_hits", "counts", "ids", "scores", "status"), g, want):
+            assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, w.view(np.uint32) if w.dtype == np.float32 else w), name
+    if os.environ.get("VQ_PROBE_MIN_DOCS") == "0" and not any(os.environ.get(k) for k in ("VQ_FORCE_GENERIC", "VQ_NO_PROBE", "VQ_NO_PROBE_OR")):
+        assert reran > 0, "no request ran again on the exact kernels: the steps never read their requests at their end"
+
+
 def test_probe_or_random_requests_with_leaf_boosts(big_corpus):
     """240 random ORs of 2-3 terms (every df of the corpus, repeated terms, leaf boosts from -2 to 20 — zero, tiny and negative ones among them —, top 1-300,
     skips up to beyond the hits) in batches: whatever k_scan_probe_or confirms and whatever it has to hand back to the exact kernels must equal the oracle

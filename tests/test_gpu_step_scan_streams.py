@@ -1,4 +1,4 @@
-"""A step that is cut in two runs its chunks on two scan streams (step_scan_stream in capi.cpp), and on an index that answers alone the next
+"""A step that is cut in two runs its chunks on two scan streams (step_scan_stream in shard_step.cpp), and on an index that answers alone the next
 step's scans no longer wait for this step's finalize.  Steps of 512 requests (the smallest a step is cut in two at, VQ_SHARD_CHUNKS=2), four of them
 driven as the benchmark drives them (step i + 1 begun before step i is ended), on a 262 144-doc corpus with the probe kernels on:
 every step's num_hits, counts, ids and scores equal vq_search_batch_flat's of the same requests bit for bit, and equal what the same steps give

@@ -14,7 +14,7 @@ NAMES = ("vq_debug_union_lists", "vq_debug_locality_lists", "vq_debug_range_hits
 
 def test_prepass_debug_entry_points_under_asan_and_ubsan(tmp_path):
     host_srcs, stubs = sanitized.host_sources()
-    assert "prepass.cpp" in host_srcs and "capi.cpp" in host_srcs and stubs
+    assert "prepass.cpp" in host_srcs and "capi.cpp" in host_srcs and "capi_debug.cpp" in host_srcs and stubs
     env = {k: v for k, v in os.environ.items() if k not in ("VQ_UNION_DENSE_MIN", "VQ_STUB_LAUNCH_LOG")}
     r, tail = sanitized.run(sanitized.build_host_check(tmp_path, "prepass_debug_check", host_srcs, stubs), env=env)
     assert r.returncode == 0 and "PREPASS_DEBUG_CHECK_OK " in r.stdout, tail
@@ -23,7 +23,7 @@ def test_prepass_debug_entry_points_under_asan_and_ubsan(tmp_path):
 
 
 def test_every_layer_names_the_entry_points():
-    for rel in ("include/veloci_amd.h", "veloci_amd/_lib.py", "INTEGRATION.md", "veloci_amd/csrc/capi.cpp", "DESIGN.md"):
+    for rel in ("include/veloci_amd.h", "veloci_amd/_lib.py", "INTEGRATION.md", "veloci_amd/csrc/capi_debug.cpp", "DESIGN.md"):
         text = open(os.path.join(ROOT, rel)).read()
         for name in NAMES:
             assert name in text, (rel, name)

@@ -32,7 +32,8 @@ def test_runners_lay_no_buffer_out_by_hand():
     assert not re.search(r"reinterpret_cast<[^>]*>\(\w+ \+ ", prepass + stayed)
     for name, text in (("prepass.cpp", prepass), ("exec.cpp", exec_cpp), ("compile.cpp", open(os.path.join(CSRC, "compile.cpp")).read()),
                        ("term_lookup.cpp", open(os.path.join(CSRC, "term_lookup.cpp")).read()),  # (these two were part of compile.cpp)
-                       ("text_requests.cpp", open(os.path.join(CSRC, "text_requests.cpp")).read()), ("capi.cpp", open(os.path.join(CSRC, "capi.cpp")).read())):
+                       ("text_requests.cpp", open(os.path.join(CSRC, "text_requests.cpp")).read()), ("capi.cpp", open(os.path.join(CSRC, "capi.cpp")).read()),
+                       ("capi_debug.cpp", open(os.path.join(CSRC, "capi_debug.cpp")).read()), ("shard_step.cpp", open(os.path.join(CSRC, "shard_step.cpp")).read())):  # (part of capi.cpp)
         assert "+ 8 + 3) / 4 * 4" not in text, name
     for fn in ("run_fuzzy_probes", "run_union_jobs", "run_range_jobs", "run_locality_jobs", "run_boost1n_jobs"):
         assert re.search(r"^void %s\(" % fn, prepass, re.M) and not re.search(r"^void %s\(" % fn, exec_cpp, re.M), fn

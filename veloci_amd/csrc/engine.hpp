@@ -24,6 +24,8 @@
 #include "hostpool.hpp"
 #include "regex_dfa.hpp"
 
+struct vq_shard_step;  // shard_step.cpp
+
 namespace vq {
 
 using vqreq::VelociError;
@@ -552,7 +554,7 @@ struct ShardComm {
     void* ctx = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev_scan[2] = {nullptr, nullptr}, ev_xchg[2] = {nullptr, nullptr}, ev_fin[2] = {nullptr, nullptr};
-    void* unmerged = nullptr;  // the step in flight whose merge is not queued yet (vq_shard_step*)
+    vq_shard_step* unmerged = nullptr;  // the step in flight whose merge is not queued yet
     int live = 0;              // steps begun and not yet ended / freed (at most two: each holds workspaces of its own)
     DevBuf gathered[2];
     DevBuf red;  // scratch of the sums-over-shards hook (u64)
@@ -613,7 +615,7 @@ struct Index {
                                        // ordering with the scan stream — and on their own stream the pre-passes of batch c+1 overlap the scan of batch c
     hipStream_t stream = nullptr;      // scans + span merges
     hipStream_t own_stream2 = nullptr;  // the second chunk of a step that is cut in two, on an index that answers alone: its upload, scans and span
-                                        // merge go here, beside the first chunk's on `stream` (step_scan_stream, capi.cpp)
+                                        // merge go here, beside the first chunk's on `stream` (step_scan_stream, shard_step.cpp)
     hipStream_t fin_stream = nullptr;  // shard merge, facet selection, result download (== stream when the caller set one)
     mutable std::mutex profile_mutex;
     mutable Profile profile;
@@ -924,6 +926,8 @@ struct PartialBatch {
     std::chrono::steady_clock::time_point t0;
     void release_workspace();
     std::vector<const vqreq::Request*> reqs;  // the batch's requests as handed in (alive until the batch is finished: a request may have to run again)
+    std::vector<std::shared_ptr<const vqreq::Request>> owners;  // ... by construction where the batch outlives the call that made it: the ABI layer
+                                                                // shares the handles' requests here.  Empty for a batch that ends inside its call
     ~PartialBatch();  // a batch given up before its merge waits for its scans: the workspace (pinned staging, blobs) is handed on only when the device is done with it
 };
 

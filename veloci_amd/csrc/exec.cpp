@@ -885,7 +885,7 @@ static void account_timed_launches(Profile& P, Workspace& ws) {
     ws.timed.clear();
 }
 
-// vq_debug_*_lists (capi.cpp): pre-pass drivers alone, on the next workspace in turn (held until `body` returns: the drivers' results live in
+// vq_debug_*_lists (capi_debug.cpp): pre-pass drivers alone, on the next workspace in turn (held until `body` returns: the drivers' results live in
 // it, `body` reads them back) and on the pre-passes' stream; their timed launches go to the profile like a batch's
 void debug_prepass(const Index& idx, const std::function<void(Workspace&, hipStream_t)>& body) {
     VQ_HIP(hipSetDevice(idx.device));
@@ -1236,7 +1236,7 @@ void debug_text_rank(const uint64_t* row_off, const uint32_t* vals, const uint32
 }
 
 // ---- the two merges alone (vq_debug_merge_spans / vq_debug_finalize): one zero-filled QHeader per job with only the fields the kernel reads,
-// ONE launch of the shipped launcher over all jobs.  The callers (capi.cpp) have checked the arguments
+// ONE launch of the shipped launcher over all jobs.  The callers (capi_debug.cpp) have checked the arguments
 namespace {
 // blobs + blob_off of the jobs' headers -> device; fill(j, header) sets job j's fields beside top_k and part_keys_off (the prefix of top_k)
 template <class Fill>

@@ -409,7 +409,8 @@ class LocalExchange:
 
 
 def shard_step_begin(index, batch):
-    """`vq_shard_step_begin`: the step's compile, scans and exchange are queued; -> handle for shard_step_end."""
+    """`vq_shard_step_begin`: the step's compile, scans and exchange are queued; -> handle for shard_step_end.  The step shares the requests with
+    their handles: `batch` may be dropped before the step is ended."""
     from . import _lib
     h = C.c_void_p()
     _lib.check(_lib.lib().vq_shard_step_begin(index.h, batch.arr, batch.n, C.byref(h)))

@@ -280,6 +280,45 @@ int vq_docset_facets(const vq_index*, const vq_docset*, const char* facets_json,
 /* measurement: with VQ_DOCSET_TIMING=1 in the environment, the HIP event time (ms) of the count kernel of this thread's last vq_docset_facets;
  * negative when none was launched or timed */
 float vq_debug_docset_facets_count_ms(void);
+/* Numeric aggregations of a staged set, computed on the device: the counterpart of vq_docset_facets for the numeric columns.  aggs_json: a
+ * non-empty list of {"field": "price"} or {"field": "price", "edges": [0, 10, 100]}; results come back in request order, the same field may occur
+ * twice.  `field` names the column "<field>.boost_valid_to_value", resolved exactly as vq_docset_from_ranges resolves it, with its errors.
+ * A field without "[]" (keyed by doc): a doc of the set without a value (below key_base, behind the last key, presence bit clear) counts in
+ * `missing`, a NaN in `nan`, everything else — the infinities included — in `count`, min, max, sum and its bucket; docs = vq_docset_len =
+ * missing + nan + count.  A field with "[]" (keyed by value id): a present value belongs to the anchor in the first entry of its
+ * "<field>.value_id_to_anchor" row (empty rows and later entries count for nothing); every present value whose anchor is in the set is
+ * aggregated, count + nan is their number, `missing` the number of docs of the set with no present value.  min / max: compared by value (-0 equals
+ * +0 and a zero is reported as +0.0); both 0 when count == 0.  sum: the exact sum of the finite counted values rounded once to f64, ties to even
+ * — bit-identical across runs, atomic orders and shardings; +inf when only positive infinities occur besides, -inf when only negative ones, NaN
+ * with both; 0.0 when nothing is counted.  edges: at most 1023 strictly ascending numbers; n_buckets = edges + 1 (0 and buckets NULL without
+ * `edges`): bucket 0 counts v < e0, bucket i e(i-1) <= v < e(i), the last v >= e(last), a stored f32 compared as f64 against the edge as written
+ * (the rule of vq_docset_from_ranges); two edges between two neighbouring f32 values leave the bucket between them empty.  The buckets add up to
+ * count, and for a column keyed by doc bucket i equals the length of the set and-ed with vq_docset_from_ranges' {gte: e(i-1), lt: e(i)} (a 1:n
+ * column counts values, a doc set docs).  VQ_ERR_JSON for text that does not
+ * parse or a value of the wrong type (an edge that is not a number); VQ_ERR_INVALID_ARGUMENT for a null argument, an empty list, an aggregation
+ * without `field`, an unknown key, more than 1023 edges, edges that do not strictly ascend, a ".token_values" column, a set of another index;
+ * the search's VQ_ERR_INDEX_NOT_FOUND for an unknown column or a 1:n field without its value_id_to_anchor store.  Synchronous; any number of
+ * threads may call concurrently, also on one set, which is only read.  VQ_NO_AGG_PREREDUCE=1 in the environment (read at every call) adds every
+ * value to the sum with atomics of its own instead of summing a wave's values first (same result); VQ_AGG_MAX_GRID=<n> (read at every call;
+ * tests) caps the workgroups per aggregation.  On a shard every rank ends with the whole
+ * set's answer: counters, buckets and the sum's limbs go through the hook of vq_index_set_allreduce in one call, min and max are agreed in four
+ * more; every rank calls in the same order, none when the whole set is empty; without the hook a shard answers
+ * VQ_ERR_UNSUPPORTED.  An unsharded index never calls the hook. */
+typedef struct vq_docset_aggs vq_docset_aggs;
+typedef struct vq_docset_agg {
+    uint64_t docs, count, missing, nan;
+    double sum;
+    float min, max;
+    uint64_t n_buckets;
+    const uint64_t* buckets; /* owned by the vq_docset_aggs */
+} vq_docset_agg;
+int vq_docset_aggregate(const vq_index*, const vq_docset*, const char* aggs_json, size_t len, vq_docset_aggs** out);
+size_t vq_docset_aggs_len(const vq_docset_aggs*);
+const vq_docset_agg* vq_docset_aggs_get(const vq_docset_aggs*, size_t i); /* NULL beyond the list */
+void vq_docset_aggs_free(vq_docset_aggs*);
+/* measurement: with VQ_DOCSET_TIMING=1 in the environment, the HIP event time (ms) of the kernels of this thread's last vq_docset_aggregate;
+ * negative when none was launched or timed */
+float vq_debug_docset_aggregate_ms(void);
 /* `SearchResult.why_found_terms` (src/search/result/search_result.rs:21-25, filled at src/search.rs:186 when the request says
  * `why_found: true`): per text index path the matched dictionary terms, as JSON {"<path>": ["term", ...]} (thread-local string;
  * the reference's map and list orders are unspecified). */

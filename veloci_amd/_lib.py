@@ -26,10 +26,17 @@ SYMBOLS = [
     "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_version",
     "vq_docset_create", "vq_docset_from_filter", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
     "vq_request_set_docset", "vq_docset_combine", "vq_docset_ids", "vq_debug_docset_route", "vq_docset_facets", "vq_debug_docset_facets_count_ms", "vq_docset_from_ranges", "vq_debug_docset_range_route",
+    "vq_docset_aggregate", "vq_docset_aggs_len", "vq_docset_aggs_get", "vq_docset_aggs_free", "vq_debug_docset_aggregate_ms",
 ]
 COMM_ID_BYTES = 128
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALLREDUCE_U32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+
+
+class DocsetAgg(C.Structure):
+    """vq_docset_agg"""
+    _fields_ = [("docs", C.c_uint64), ("count", C.c_uint64), ("missing", C.c_uint64), ("nan", C.c_uint64), ("sum", C.c_double), ("min", C.c_float), ("max", C.c_float),
+                ("n_buckets", C.c_uint64), ("buckets", C.POINTER(C.c_uint64))]
 
 
 class VelociError(RuntimeError):
@@ -173,6 +180,11 @@ def lib():
         "vq_debug_docset_facets_count_ms": (C.c_float, []),
         "vq_docset_from_ranges": (i, [vp, C.c_char_p, C.c_size_t, vp, C.POINTER(vp)]),
         "vq_debug_docset_range_route": (i, [vp]),
+        "vq_docset_aggregate": (i, [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(vp)]),
+        "vq_docset_aggs_len": (sz, [vp]),
+        "vq_docset_aggs_get": (C.POINTER(DocsetAgg), [vp, sz]),
+        "vq_docset_aggs_free": (None, [vp]),
+        "vq_debug_docset_aggregate_ms": (C.c_float, []),
     }
     for name, (rt, at) in sig.items():
         f = getattr(L, name)

@@ -619,6 +619,28 @@ int vq_docset_facets(const vq_index* index, const vq_docset* d, const char* face
     });
 }
 float vq_debug_docset_facets_count_ms(void) { return vq::docset_facets_last_count_ms(); }
+int vq_docset_aggregate(const vq_index* index, const vq_docset* d, const char* aggs_json, size_t len, vq_docset_aggs** out) {
+    return guard([&] {
+        if (!index || !d || !aggs_json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_aggregate: null argument");
+        *out = nullptr;
+        std::vector<vq::AggSpec> specs;
+        try {
+            specs = vq::agg_specs_from_json(vqjson::parse(aggs_json, len));
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        const std::shared_ptr<const DocSet> set = d->set;  // held for the length of the call
+        auto h = std::make_unique<vq_docset_aggs>();
+        h->r = vq::docset_aggregate(*index->idx, *set, specs);
+        for (const vq::AggResult& a : h->r)
+            h->c.push_back(vq_docset_agg{a.docs, a.count, a.missing, a.nan, a.sum, a.min, a.max, uint64_t(a.buckets.size()), a.buckets.empty() ? nullptr : a.buckets.data()});
+        *out = h.release();
+    });
+}
+size_t vq_docset_aggs_len(const vq_docset_aggs* a) { return a ? a->c.size() : 0; }
+const vq_docset_agg* vq_docset_aggs_get(const vq_docset_aggs* a, size_t i) { return a && i < a->c.size() ? &a->c[i] : nullptr; }
+void vq_docset_aggs_free(vq_docset_aggs* a) { delete a; }
+float vq_debug_docset_aggregate_ms(void) { return vq::docset_aggregate_last_ms(); }
 int vq_debug_docset_route(const vq_docset* d) { return d ? d->set->route : -1; }
 uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
 uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }

@@ -25,6 +25,10 @@ struct vq_docset {
 struct vq_result {
     vq::Result r;
 };
+struct vq_docset_aggs {
+    std::vector<vq::AggResult> r;  // the buckets the C structs point into
+    std::vector<vq_docset_agg> c;
+};
 struct vq_partial_batch {
     std::unique_ptr<vq::PartialBatch> pb;
 };

@@ -17,14 +17,7 @@ uint32_t bits_of(float f) {
     std::memcpy(&b, &f, 4);
     return b;
 }
-// the smallest f32 (infinities included) that is >= b / the largest that is <= b.  b is no NaN (JSON has none)
-float f32_at_or_above(double b) {
-    if (b > double(FLT_MAX)) return HUGE_VALF;
-    if (b < -double(FLT_MAX)) return std::isinf(b) ? -HUGE_VALF : -FLT_MAX;
-    float f = float(b);
-    if (double(f) < b) f = std::nextafterf(f, HUGE_VALF);
-    return f;
-}
+// the largest f32 (infinities included) that is <= b.  b is no NaN (JSON has none)
 float f32_at_or_below(double b) {
     if (b < -double(FLT_MAX)) return -HUGE_VALF;
     if (b > double(FLT_MAX)) return std::isinf(b) ? HUGE_VALF : FLT_MAX;
@@ -33,6 +26,37 @@ float f32_at_or_below(double b) {
     return f;
 }
 
+}  // namespace
+
+// the smallest f32 (infinities included) that is >= b (engine.hpp: the aggregations' edges use it too)
+float f32_at_or_above(double b) {
+    if (b > double(FLT_MAX)) return HUGE_VALF;
+    if (b < -double(FLT_MAX)) return std::isinf(b) ? -HUGE_VALF : -FLT_MAX;
+    float f = float(b);
+    if (double(f) < b) f = std::nextafterf(f, HUGE_VALF);
+    return f;
+}
+
+// the column a clause or an aggregation names, resolved as the request-level boosts resolve it (compile.cpp: anchor-level column boosts)
+RangeColumn resolve_range_column(const Index& idx, const std::string& field, const char* what) {
+    if (field.find(TOKEN_VALUES) != std::string::npos) throw VelociError(vqreq::ERR_INVALID_ARGUMENT, std::string(what) + ": " + field + " is keyed by term ids, not by docs");
+    const auto it = idx.boost.find(field + BOOST_VALID_TO_VALUE);
+    if (it == idx.boost.end()) throw VelociError(vqreq::ERR_INDEX_NOT_FOUND, "Did not found path in indices " + field + BOOST_VALID_TO_VALUE);
+    RangeColumn col;
+    col.d = RangeClauseD{};
+    col.d.values = it->second.values.as<uint32_t>();
+    col.d.present = it->second.has_present ? it->second.present.as<uint32_t>() : nullptr;
+    col.d.key_base = it->second.key_base;
+    col.d.num_keys = it->second.num_keys;
+    if (field.find("[]") != std::string::npos) {
+        const auto kit = idx.kv.find(field + VALUE_ID_TO_ANCHOR);
+        if (kit == idx.kv.end() || !kit->second.value_csr) throw VelociError(vqreq::ERR_INDEX_NOT_FOUND, "Did not found path in indices " + field + VALUE_ID_TO_ANCHOR);
+        col.to_anchor = &kit->second;
+    }
+    return col;
+}
+
+namespace {
 double bound_of(const vqjson::Value& clause, const char* key, bool* has) {
     const vqjson::Value* v = clause.get(key);
     *has = v && !v->is_null();
@@ -104,24 +128,12 @@ std::shared_ptr<const DocSet> make_docset_from_ranges(const Index& idx, const st
     std::vector<OneToN> one_to_n;
     for (size_t i = 0; i < clauses.size(); ++i) {
         const RangeClause& c = clauses[i];
-        if (c.field.find(TOKEN_VALUES) != std::string::npos)
-            throw VelociError(vqreq::ERR_INVALID_ARGUMENT, "doc set from ranges: " + c.field + " is keyed by term ids, not by docs");
-        // the column, resolved as the request-level boosts resolve it (compile.cpp: anchor-level column boosts)
-        const auto it = idx.boost.find(c.field + BOOST_VALID_TO_VALUE);
-        if (it == idx.boost.end()) throw VelociError(vqreq::ERR_INDEX_NOT_FOUND, "Did not found path in indices " + c.field + BOOST_VALID_TO_VALUE);
+        const RangeColumn col = resolve_range_column(idx, c.field, "doc set from ranges");
         RangeClauseD& d = descs[i];
-        d = RangeClauseD{};
-        d.values = it->second.values.as<uint32_t>();
-        d.present = it->second.has_present ? it->second.present.as<uint32_t>() : nullptr;
-        d.key_base = it->second.key_base;
-        d.num_keys = it->second.num_keys;
+        d = col.d;
         d.missing = c.missing ? 1u : 0u;
         range_clause_keys(c, &d.lo, &d.hi);
-        if (c.field.find("[]") != std::string::npos) {
-            const auto kit = idx.kv.find(c.field + VALUE_ID_TO_ANCHOR);
-            if (kit == idx.kv.end() || !kit->second.value_csr) throw VelociError(vqreq::ERR_INDEX_NOT_FOUND, "Did not found path in indices " + c.field + VALUE_ID_TO_ANCHOR);
-            one_to_n.push_back(OneToN{i, d, &kit->second});
-        }
+        if (col.to_anchor) one_to_n.push_back(OneToN{i, d, col.to_anchor});
     }
     if (!idx.can_sum_over_shards())  // the result's length is a sum over the shards
         throw VelociError(vqreq::ERR_UNSUPPORTED, "unsupported on the MI355X query path: doc set from ranges on a sharded index without vq_index_set_allreduce");

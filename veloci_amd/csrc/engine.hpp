@@ -689,6 +689,43 @@ std::vector<RangeClause> range_clauses_from_json(const vqjson::Value& v);
 // [lo, hi] of range_key values a clause's bounds select, cut to [kRangeKeyMin, kRangeKeyMax]; lo > hi: nothing
 void range_clause_keys(const RangeClause& c, uint32_t* lo, uint32_t* hi);
 std::shared_ptr<const DocSet> make_docset_from_ranges(const Index& idx, const std::vector<RangeClause>& clauses, std::shared_ptr<const DocSet> within);
+// The column "<field>.boost_valid_to_value" as the kernels take it (values, presence, key_base, num_keys; the rest of d zero) and, for a field
+// with "[]", its "<field>.value_id_to_anchor" table (null: the column is keyed by doc).  make_docset_from_ranges and docset_aggregate share it:
+// ERR_INVALID_ARGUMENT ("<what>: ... keyed by term ids") for a ".token_values" column, the search's ERR_INDEX_NOT_FOUND for an unknown column or a
+// 1:n field without its table
+struct RangeColumn {
+    RangeClauseD d;
+    const KVStore* to_anchor = nullptr;
+};
+RangeColumn resolve_range_column(const Index& idx, const std::string& field, const char* what);
+float f32_at_or_above(double b);  // the smallest f32 (infinities included) that is >= b (no NaN)
+
+// Numeric aggregations of a staged set (docset_aggs.cpp, docset_aggs.hip): per spec the set's docs (docs = DocSet::len), the present non-NaN values
+// (count), the docs without a value (missing), the NaNs (nan), min / max compared through range_key (a zero is +0.0; 0 when count == 0), the exact
+// sum of the finite counted values rounded once to f64 (+-inf / NaN by the infinities counted, 0.0 when nothing is), and with `edges` the
+// len(edges) + 1 bucket counts: bucket b holds the values with exactly b edges e for which (double)v >= e.  Synchronous, on pre_stream (else
+// stream); each call owns its state.  On a shard counters, buckets and limbs are summed in one call of Index::sum_over_shards, min / max agreed
+// in four more (one-hot digit histograms of the keys' bytes, most significant first); ERR_UNSUPPORTED without the hook
+struct AggSpec {
+    std::string field;
+    bool has_edges = false;
+    std::vector<double> edges;
+};
+struct AggResult {
+    uint64_t docs = 0, count = 0, missing = 0, nan = 0;
+    double sum = 0.0;
+    float min = 0.0f, max = 0.0f;
+    std::vector<uint64_t> buckets;  // empty: the spec had no `edges`
+};
+// the spec list of vq_docset_aggregate: throws vqjson::ParseError for a value of the wrong type, ERR_INVALID_ARGUMENT for an empty list, a spec
+// without `field`, an unknown key, more than kAggMaxEdges edges or edges that do not strictly ascend
+std::vector<AggSpec> agg_specs_from_json(const vqjson::Value& v);
+std::vector<AggResult> docset_aggregate(const Index& idx, const DocSet& ds, const std::vector<AggSpec>& specs);
+// (pos - neg) * 2^-149 rounded once to f64, ties to even: pos / neg are 9 slots each, slot i weighs 2^(32 i) and may hold any u64 (carries are
+// propagated here)
+double agg_limbs_to_double(const uint64_t* pos, const uint64_t* neg);
+// VQ_DOCSET_TIMING=1: the HIP event time (ms) of the kernels of this thread's last docset_aggregate; negative: none was launched or timed
+float docset_aggregate_last_ms();
 // The set's local ids (sorted, unique, unpadded): min(local_len, cap) of them to `out`, host memory or (on_device) memory of the set's GPU — then
 // device to device on the set's stream, finished on return.  Returns local_len
 uint64_t copy_docset_ids(const DocSet& ds, uint32_t* out, uint64_t cap, bool on_device);

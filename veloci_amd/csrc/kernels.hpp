@@ -263,6 +263,42 @@ void launch_range_probe(hipStream_t st, const uint32_t* ids, uint32_t len, const
 // [doc_lo, doc_hi) set nothing
 void launch_range_scatter(hipStream_t st, const RangeClauseD& column, const uint64_t* a_off, const uint32_t* a_vals, uint32_t a_key_base, uint32_t a_num_keys, uint32_t doc_lo,
                           uint32_t doc_hi, uint32_t* in_bits, uint32_t* has_bits);
+// ---- numeric aggregations of a doc set (docset_aggs.hip): counters, min / max keys, an exact sum and range-bucket counts of f32 columns over a
+// staged set.  An aggregation's state is kAggBuckets + n_edges + 1 u64 slots from state[state_off] on (zeroed before the launch):
+//   kAggCount    present non-NaN values (the infinities included)      kAggHas   1:n only: docs of the set with a present value
+//   kAggNan      present NaNs                                          kAggMissing   anchor-keyed only: docs of the set without a value
+//   kAggPosInf / kAggNegInf   the infinities among kAggCount
+//   kAggLimbs    the exact sum of the finite values: 9 limbs of the positive values, then 9 of the negative ones.  A finite non-zero f32 is
+//                m * 2^(s - 149), m < 2^24, s = max(biased exponent, 1) - 1 in [0, 253]; w = (u64)m << (s & 31) adds w & 0xFFFFFFFF to limb s >> 5
+//                and w >> 32 to the next: the limbs weigh 2^(32 i - 149).  An addend is below 2^32 and a set holds fewer than 2^32 values: no slot
+//                overflows, every sum is an integer, the result does not depend on the order of the atomics
+//   kAggBuckets  bucket b = the values with exactly b edge keys <= range_key(value): edges (device memory, n_edges <= kAggMaxEdges) ascend
+// and mm[mm_off] / mm[mm_off + 1] are the smallest / largest range_key counted (0xFFFFFFFF / 0 before the launch).
+constexpr uint32_t kAggMaxEdges = 1023;
+constexpr uint32_t kAggCount = 0, kAggMissing = 1, kAggHas = 1, kAggNan = 2, kAggPosInf = 3, kAggNegInf = 4, kAggLimbs = 5, kAggLimbsPerSign = 9;
+constexpr uint32_t kAggBuckets = kAggLimbs + 2 * kAggLimbsPerSign;
+struct DocsetAggD {
+    const uint32_t* values;   // the column's f32 bit patterns (1:n: 16-byte aligned, a vector of slack behind them)
+    const uint32_t* present;  // presence bitmap over the rows, or null: every row is present
+    const uint32_t* edges;    // n_edges ascending range_key values
+    const uint64_t* a_off;    // 1:n: the value_id_to_anchor table (row r = value id a_key_base + r), the first entry of a row is the value's anchor
+    const uint32_t* a_vals;
+    uint32_t* has_bits;       // 1:n: a zeroed bitmap of the scratch bitmap's shape (word doc >> 5)
+    uint32_t key_base, num_keys;
+    uint32_t a_key_base, a_num_keys;
+    uint32_t n_edges, state_off, mm_off, pad;
+};
+// anchor-keyed columns (row = id - key_base; no value: id < key_base, row >= num_keys, presence bit clear): workgroup (x, f) aggregates aggs[f]
+// over its stride of the set's local ids (docs: sorted, 16-byte aligned, padded to a multiple of 4 entries).  prereduce: the sum's addends of a
+// wave's round are added up per limb across the wave before they reach LDS; false: one LDS atomic pair per value.  Nothing is launched for an
+// empty set or list.  max_grid: workgroups per aggregation at most (0: kAggMaxGrid, docset_aggs.hip)
+void launch_docset_agg_ids(hipStream_t st, const uint32_t* docs, uint32_t local_len, const DocsetAggD* aggs, uint32_t m, unsigned long long* state, uint32_t* mm, bool prereduce,
+                           uint32_t max_grid = 0);
+// 1:n columns (keyed by value id): workgroup (x, f) streams its stride of aggs[f]'s column; a present value whose anchor lies in [doc_lo, doc_hi)
+// and in `member` (bit of doc d in word (d >> 5) - member_word0) is aggregated, and sets its anchor's bit in has_bits: the first to set it counts
+// the doc in kAggHas.  max_keys: the largest num_keys of the m columns
+void launch_docset_agg_values(hipStream_t st, const DocsetAggD* aggs, uint32_t m, uint32_t max_keys, const uint32_t* member, uint32_t member_word0, uint32_t doc_lo,
+                              uint32_t doc_hi, unsigned long long* state, uint32_t* mm, bool prereduce, uint32_t max_grid = 0);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

@@ -242,6 +242,42 @@ class DocSet:
         """-> {field: [(value, count)]}, the form of `SearchResult.facets` (None for an empty facet list); see `facet_result`"""
         return self.facet_result(facets).facets
 
+    def aggregate(self, specs):
+        """Numeric aggregations of the set's docs (`vq_docset_aggregate`), computed on the index's GPU.  `specs`: a non-empty list of
+        {"field": "price"} or {"field": "price", "edges": [0, 10, 100]} (or JSON text).  -> one dict per spec, in request order: `docs` (len(self)),
+        `count` (present non-NaN values), `missing` (docs without a value), `nan`, `min`, `max` (None when count == 0), `sum` (the exact sum of the
+        finite values rounded once to float64: math.fsum's answer, the same on every run and sharding; +-inf / NaN by the infinities counted) and,
+        with `edges`, `buckets`: len(edges) + 1 ints, bucket i counting e(i-1) <= v < e(i) as `from_range(gte=, lt=)` compares.  On a shard every
+        rank gets the whole set's answer through `index.set_allreduce`'s hook."""
+        if not isinstance(specs, (str, bytes)):
+            specs = json.dumps(list(specs), allow_nan=False)  # (JSON has no infinity: an edge beyond the floats goes in as text, e.g. 1e999)
+        if isinstance(specs, str):
+            specs = specs.encode()
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_aggregate(self.index.h, self._handle(), specs, len(specs), C.byref(h)))
+        try:
+            out = []
+            for i in range(int(self.L.vq_docset_aggs_len(h))):
+                a = self.L.vq_docset_aggs_get(h, i).contents
+                d = {"docs": int(a.docs), "count": int(a.count), "missing": int(a.missing), "nan": int(a.nan), "min": float(a.min) if a.count else None,
+                     "max": float(a.max) if a.count else None, "sum": float(a.sum)}
+                if a.n_buckets:
+                    d["buckets"] = [int(a.buckets[b]) for b in range(int(a.n_buckets))]
+                out.append(d)
+            return out
+        finally:
+            self.L.vq_docset_aggs_free(h)
+
+    def stats(self, field):
+        """-> dict(docs, count, missing, nan, min, max, sum, mean) of one column over the set; min, max and mean are None when count == 0"""
+        d = self.aggregate([{"field": field}])[0]
+        d["mean"] = d["sum"] / d["count"] if d["count"] else None
+        return d
+
+    def histogram(self, field, edges):
+        """-> len(edges) + 1 ints: the set's values of `field` below edges[0], in [edges[i-1], edges[i]), at or above edges[-1]"""
+        return self.aggregate([{"field": field, "edges": [float(e) for e in edges]}])[0]["buckets"]
+
     def timings(self):
         """(mark, count + scan, expand) in ms, recorded when the set was made with VQ_DOCSET_TIMING=1 in the environment; else None"""
         a, b, c = C.c_float(), C.c_float(), C.c_float()

@@ -515,6 +515,18 @@ const char* vq_profile_json(const vq_index*, int reset);
  * 0xFFFFFFFF when no device is available. */
 uint32_t vq_debug_div100_mismatches(void);
 
+/* The column boost of the scans (add_boost, boost.rs:470-504: skip_when_score, the row of the doc, boost function, expression) alone, one lane
+ * per element, through the very device functions the scan kernels call: out_scores[i] = the boost applied to scores[i] for doc docs[i];
+ * out_log10_factor[i] = the f32 log10(value + param) an explain record carries for a Log10 boost, for every doc with a present row whatever the
+ * function and the skip rule, 0.0f for a doc without one.  fun: -1 none, 0 Log2, 1 Log10, 2 Multiply, 3 Add, 4 Replace; `expression` (or NULL)
+ * and the n_skip (0 .. 4) `skip` values are parsed as a request's `expression` / `skip_when_score`.  The column covers docs key_base .. key_base
+ * + num_keys - 1: `values` holds num_keys f32, `present_words` (or NULL: every row present) (num_keys + 31) / 32 words, bit r & 31 of word r >> 5
+ * set for a present row r.  n in 1 .. 2^24, num_keys at most 2^24.  0; -1 without a device; -2 for arguments outside these ranges or a boost
+ * the request parser refuses (vq_last_error says which). */
+int vq_debug_col_boost(int fun, float param, const char* expression, const float* skip, uint32_t n_skip, const float* values, uint32_t num_keys,
+                       const uint32_t* present_words, uint32_t key_base, const uint32_t* docs, const float* scores, uint32_t n, float* out_scores,
+                       float* out_log10_factor);
+
 /* Requests of this index that were run a second time on the exact kernels because the short cut of a speculative one could not be confirmed:
  * an OR of the shape k_scan_probe_or takes ranks only the docs that hold its rarest term and is confirmed by the k-th key it returns. */
 uint64_t vq_index_speculative_reruns(const vq_index*);

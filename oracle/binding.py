@@ -37,6 +37,9 @@ def lib():
         L.vo_index_add_phrase_pair_to_anchor.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vo_index_add_boost.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.vo_index_set_column_meta.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
+        L.vo_index_set_boost_log.argtypes = [C.c_void_p, C.c_int]
+        L.vo_op_boost_log.restype = None
+        L.vo_op_boost_log.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p]
         L.vo_search_json.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
         for name, rt in [("num_hits", C.c_uint64), ("execution_time_ns", C.c_uint64), ("len", C.c_size_t), ("ids", u32p), ("scores", f32p),
                          ("num_facets", C.c_size_t)]:
@@ -151,6 +154,13 @@ class OracleIndex:
 
     def set_column_meta(self, field, is_anchor_identity_column, tokenize=True):
         self.L.vo_index_set_column_meta(self.h, field.encode(), int(is_anchor_identity_column), int(tokenize))
+
+    def set_boost_log(self, mode):
+        """How the search's boost stage (request-level column boosts, the 1:n anchor boost) takes the logarithm of Log10 / Log2: "libm" (the
+        default: log10f / log2f, as the reference links them) or "f64" (the f64 logarithm rounded to f32, the product's device definition).
+        token_value boosts, index-time scores and the distance scores use libm in both modes."""
+        if self.L.vo_index_set_boost_log(self.h, _BOOST_LOG[mode]) != 0:
+            raise ValueError(mode)
 
     def search_json(self, js):
         if not isinstance(js, (bytes, bytearray)):
@@ -300,6 +310,17 @@ def apply_boost_values_anchor(hits, boosts, boost_fun=None, param=None, expressi
                                               C.c_float(param or 0.0), int(param is not None), expression.encode() if expression else None,
                                               _p(oi, u32p), _p(osc, f32p))
     return _hits(n, oi, osc)
+
+
+_BOOST_LOG = {"libm": 0, "f64": 1}
+
+
+def boost_log(fun, x, mode="libm"):
+    """The logarithm a "Log10" / "Log2" boost takes of the f32 array x under OracleIndex.set_boost_log(mode) -> f32 array"""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros(len(x), np.float32)
+    lib().vo_op_boost_log(int({"Log10": True, "Log2": False}[fun]), _BOOST_LOG[mode], len(x), _p(x, f32p), _p(out, f32p))
+    return out
 
 
 def top_n_sort(hits, top_n):

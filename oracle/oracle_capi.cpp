@@ -36,6 +36,12 @@ void* vo_index_new(uint32_t num_anchors) {
     return i;
 }
 void vo_index_free(void* p) { delete static_cast<Index*>(p); }
+// mode 0: libm (the default), 1: f64 — see BoostLog.  -1 for any other mode
+int vo_index_set_boost_log(void* p, int mode) {
+    if (mode != 0 && mode != 1) return -1;
+    static_cast<Index*>(p)->boost_log = mode ? BoostLog::F64 : BoostLog::Libm;
+    return 0;
+}
 
 int vo_index_add_fst(void* p, const char* path, uint32_t num_terms, const uint8_t* bytes, const uint64_t* offsets) {
     Fst f;
@@ -372,6 +378,10 @@ uint32_t vo_op_apply_boost_values_anchor(uint32_t nh, const uint32_t* ids, const
     if (expression) bp.expression = std::string(expression);
     apply_boost_values_anchor(a[0], bp, b);
     return hits_out(a[0], out_ids, out_scores);
+}
+// the logarithm a Log10 (base10 != 0) / Log2 boost takes of x[i] under log mode 0 (libm) / 1 (f64)
+void vo_op_boost_log(int base10, int mode, uint32_t n, const float* x, float* out) {
+    for (uint32_t i = 0; i < n; ++i) out[i] = boost_logarithm(base10 != 0, x[i], mode ? BoostLog::F64 : BoostLog::Libm);
 }
 uint32_t vo_op_top_n_sort(uint32_t nh, const uint32_t* ids, const float* scores, uint32_t top_n, uint32_t* out_ids, float* out_scores) {
     std::vector<Hit> v;

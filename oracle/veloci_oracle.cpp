@@ -348,7 +348,7 @@ SearchFieldResult get_term_ids_in_field(const Index& index, PlanRequestSearchPar
         RequestBoostPart tb = *req.token_value;
         tb.path = tb.path + TEXTINDEX + TOKEN_VALUES;
         req.token_value->path = tb.path;
-        add_boost(index, tb, result);
+        add_boost(index, tb, result);  // (libm in both log modes: the product takes token_value boosts on the host, with libm)
     }
     return result;
 }
@@ -903,15 +903,23 @@ float score_expression(const std::string& expression, float rank) {  // expressi
     }
 }
 
+// The logarithm of a Log10 / Log2 boost.  BoostLog::Libm: log10f / log2f as the reference links them.  BoostLog::F64: the f64 logarithm rounded to
+// f32 — the definition the product's device code uses for column boosts (on every input measured the correctly rounded f32 result; libm's
+// differs from it by up to 2 ulp for log10f, 1 ulp for log2f).
+float boost_logarithm(bool base10, float x, BoostLog mode) {
+    if (mode == BoostLog::F64) return base10 ? float(std::log10(double(x))) : float(std::log2(double(x)));
+    return base10 ? std::log10(x) : std::log2(x);
+}
+
 void apply_boost(Hit& hit, float boost_value, float boost_param, const std::optional<BoostFunction>& f, const std::optional<std::string>& expre,
-                 ExplainMap* explain) {  // :283-377
+                 ExplainMap* explain, BoostLog log_mode) {  // :283-377
     if (f) {
         switch (*f) {
             case BoostFunction::Log10:
-                push_boost_record(explain, hit.id, std::log10(boost_value + boost_param));  // :297-300 (only this function records its factor)
-                hit.score *= std::log10(boost_value + boost_param);
+                push_boost_record(explain, hit.id, boost_logarithm(true, boost_value + boost_param, log_mode));  // :297-300 (only this function records its factor)
+                hit.score *= boost_logarithm(true, boost_value + boost_param, log_mode);
                 break;
-            case BoostFunction::Log2: hit.score *= std::log2(boost_value + boost_param); break;
+            case BoostFunction::Log2: hit.score *= boost_logarithm(false, boost_value + boost_param, log_mode); break;
             case BoostFunction::Multiply: hit.score *= boost_value + boost_param; break;
             case BoostFunction::Add: hit.score += boost_value + boost_param; break;
             case BoostFunction::Replace: hit.score = boost_value + boost_param; break;
@@ -921,7 +929,7 @@ void apply_boost(Hit& hit, float boost_value, float boost_param, const std::opti
     push_boost_record(explain, hit.id, hit.score);  // :371-374: the score after the boost
 }
 
-void apply_boost_values_anchor(SearchFieldResult& results, const RequestBoostPart& boost, const std::vector<Hit>& boost_values) {  // :255-281
+void apply_boost_values_anchor(SearchFieldResult& results, const RequestBoostPart& boost, const std::vector<Hit>& boost_values, BoostLog log_mode) {  // :255-281
     float boost_param = boost.param.value_or(0.0f);
     ExplainMap* explain = is_explain(results.request) ? &results.explain : nullptr;  // :258
     size_t pos = 0;
@@ -941,17 +949,17 @@ void apply_boost_values_anchor(SearchFieldResult& results, const RequestBoostPar
                         break;
                     } else if (b_hit.id == hit.id) {
                         hit_curr = b_hit;
-                        apply_boost(hit, b_hit.score, boost_param, boost.boost_fun, boost.expression, explain);
+                        apply_boost(hit, b_hit.score, boost_param, boost.boost_fun, boost.expression, explain, log_mode);
                     }
                 }
             } else if (hit_curr.id == hit.id) {
-                apply_boost(hit, hit_curr.score, boost_param, boost.boost_fun, boost.expression, explain);
+                apply_boost(hit, hit_curr.score, boost_param, boost.boost_fun, boost.expression, explain, log_mode);
             }
         }
     }
 }
 
-void add_boost(const Index& index, const RequestBoostPart& boost, SearchFieldResult& hits) {  // :470-504
+void add_boost(const Index& index, const RequestBoostPart& boost, SearchFieldResult& hits, BoostLog log_mode) {  // :470-504
     const BoostStore& store = index.get_boost(boost.path + BOOST_VALID_TO_VALUE);
     float boost_param = boost.param.value_or(0.0f);
     std::vector<float> skip_when_score = boost.skip_when_score.value_or(std::vector<float>{});
@@ -969,7 +977,7 @@ void add_boost(const Index& index, const RequestBoostPart& boost, SearchFieldRes
             float boost_value;
             uint32_t bits = *v;
             std::memcpy(&boost_value, &bits, 4);
-            apply_boost(hit, boost_value, boost_param, boost.boost_fun, boost.expression, explain);
+            apply_boost(hit, boost_value, boost_param, boost.boost_fun, boost.expression, explain, log_mode);
         }
     }
 }
@@ -1242,7 +1250,7 @@ struct PlanCtx {
                 fr = join_to_parent_ids(fr, part.path + TEXTINDEX + VALUE_ID_TO_PARENT);
                 get_boost_ids_and_resolve_to_anchor(boosto[0]->path, fr);
                 // ApplyAnchorBoost plan_steps.rs:203-219
-                apply_boost_values_anchor(token_to_anchor, *boosto[0], fr.boost_ids);
+                apply_boost_values_anchor(token_to_anchor, *boosto[0], fr.boost_ids, index.boost_log);
                 return token_to_anchor;
             }
         }
@@ -1341,7 +1349,7 @@ SearchResult search(Request request, const Index& index) {
     if (filter_res) res = intersect_score_hits_with_ids(std::move(res), *filter_res);  // :163-173
     if (request.boost) {  // :175-189 anchor-level boosts (paths without [])
         for (auto& b : *request.boost)
-            if (b.path.find("[]") == std::string::npos) add_boost(index, b, res);
+            if (b.path.find("[]") == std::string::npos) add_boost(index, b, res, index.boost_log);
     }
     if (request.phrase_boosts) {  // :191-193, :202-262; plan_steps.rs:235-293
         std::vector<SearchFieldResult> boosts;

@@ -227,8 +227,15 @@ struct ColumnMeta {
     bool tokenize = true;
 };
 
+// How the search's boost stage (request-level column boosts, the 1:n anchor boost) takes the logarithm of Log10 / Log2: libm's f32 functions as the
+// reference links them, or the f64 logarithm rounded to f32 as the product's device code does.  token_value boosts, index-time scores and
+// get_default_score_for_distance use libm in both modes (the product computes those on the host with libm too).
+enum class BoostLog { Libm, F64 };
+float boost_logarithm(bool base10, float x, BoostLog mode);
+
 struct Index {
     uint32_t num_anchors = 0;
+    BoostLog boost_log = BoostLog::Libm;
     std::map<std::string, Fst> fst;
     std::map<std::string, TokenToAnchorScore> token_to_anchor_score;
     std::map<std::string, KeyValueStore> key_value_stores;
@@ -293,9 +300,10 @@ std::vector<Hit> boost_text_locality_all(const Index&, TermIdHits& term_id_hits_
 // A10
 float score_expression(const std::string& expression, float rank);  // expression.rs:26-95
 void apply_boost(Hit& hit, float boost_value, float boost_param, const std::optional<BoostFunction>& f,
-                 const std::optional<std::string>& expre, ExplainMap* explain = nullptr);  // boost.rs:283-377
-void apply_boost_values_anchor(SearchFieldResult& results, const RequestBoostPart& boost, const std::vector<Hit>& boost_values);  // boost.rs:255-281
-void add_boost(const Index&, const RequestBoostPart& boost, SearchFieldResult& hits);  // boost.rs:470-504
+                 const std::optional<std::string>& expre, ExplainMap* explain = nullptr, BoostLog log_mode = BoostLog::Libm);  // boost.rs:283-377
+void apply_boost_values_anchor(SearchFieldResult& results, const RequestBoostPart& boost, const std::vector<Hit>& boost_values,
+                               BoostLog log_mode = BoostLog::Libm);  // boost.rs:255-281
+void add_boost(const Index&, const RequestBoostPart& boost, SearchFieldResult& hits, BoostLog log_mode = BoostLog::Libm);  // boost.rs:470-504
 // A11
 std::vector<Hit> top_n_sort(std::vector<Hit> data, uint32_t top_n);  // sort.rs:5-22
 // A12

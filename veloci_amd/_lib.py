@@ -23,7 +23,7 @@ SYMBOLS = [
     "vq_search_batch_partial_at", "vq_partial_slots", "vq_index_partial_arena_ptr", "vq_partial_total_bytes", "vq_merge_partials_flat_strided",
     "vq_comm_unique_id", "vq_comm_init", "vq_comm_init_custom", "vq_comm_destroy", "vq_shard_step_begin", "vq_shard_step_end", "vq_shard_step_free", "vq_shard_step_flat",
     "vq_profile_read", "vq_profile_enable", "vq_profile_json", "vq_debug_div100_mismatches", "vq_debug_facet_select", "vq_debug_merge_spans", "vq_debug_finalize", "vq_index_speculative_reruns", "vq_index_suggest_topn_probes", "vq_debug_dict_topn", "vq_index_highlight_rank_counts", "vq_debug_text_rank", "vq_debug_union_lists", "vq_debug_locality_lists",
-    "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_version",
+    "vq_debug_range_hits", "vq_debug_boost1n_lists", "vq_debug_node_counts", "vq_debug_col_boost", "vq_version",
     "vq_docset_create", "vq_docset_from_filter", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
     "vq_request_set_docset", "vq_docset_combine", "vq_docset_ids", "vq_debug_docset_route", "vq_docset_facets", "vq_debug_docset_facets_count_ms", "vq_docset_from_ranges", "vq_debug_docset_range_route",
     "vq_docset_aggregate", "vq_docset_aggs_len", "vq_docset_aggs_get", "vq_docset_aggs_free", "vq_debug_docset_aggregate_ms",
@@ -134,6 +134,7 @@ def lib():
         "vq_profile_json": (cp, [vp, i]),
         "vq_debug_div100_mismatches": (u32, []),
         "vq_debug_facet_select": (i, [vp, u32, u32, u32, vp, vp]),
+        "vq_debug_col_boost": (i, [i, C.c_float, cp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp]),
         "vq_debug_merge_spans": (i, [vp, vp, vp, u32, vp]),
         "vq_debug_finalize": (i, [vp, vp, u32, C.c_size_t, vp, u32, vp, vp, vp, vp]),
         "vq_index_speculative_reruns": (u64, [vp]),

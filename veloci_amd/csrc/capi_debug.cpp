@@ -4,8 +4,18 @@
 #include <cstring>
 
 #include "capi_internal.hpp"
+#include "term_lookup.hpp"
 
 using namespace vq;
+
+#ifndef __HIPCC__
+// A host build of this file (the stubbed device layer, csrc/Makefile `asan` / `hoststub`) has no kernels.hip behind vq_debug_col_boost.  Its
+// launcher comes from the stub files of the tests tree (tests/native/hip_stub_col_boost.cpp); a tree of stubs from before the hook has none,
+// and the host build must still link: this weak definition declines like a stub, and any other definition takes its place.
+namespace vq {
+__attribute__((weak)) int debug_col_boost(DColBoost, const float*, uint32_t, const uint32_t*, uint32_t, const uint32_t*, const float*, uint32_t, float*, float*) { return -1; }
+}  // namespace vq
+#endif
 
 // ---- helpers of the vq_debug_*_lists functions below
 namespace {
@@ -106,6 +116,28 @@ int vq_debug_text_rank(const uint64_t* row_off, const uint32_t* row_vals, const 
         return -1;
     }
     return 0;
+}
+/* self-check (tests): the scans' column boost (apply_col_boost) alone on a caller's column, docs and scores; the boost is parsed as the compiler
+   parses a request's (fill_boost_params).  0; -1 without a device; -2 for arguments the parse or the kernel does not take */
+int vq_debug_col_boost(int fun, float param, const char* expression, const float* skip, uint32_t n_skip, const float* values, uint32_t num_keys,
+                       const uint32_t* present_words, uint32_t key_base, const uint32_t* docs, const float* scores, uint32_t n, float* out_scores,
+                       float* out_log10_factor) {
+    if (fun < BF_NONE || fun > BF_REPLACE || (n_skip && !skip) || (num_keys && !values) || !docs || !scores || !out_scores || !out_log10_factor || n == 0 ||
+        n > (uint32_t(1) << 24) || num_keys > (uint32_t(1) << 24) || uint64_t(key_base) + num_keys > 0xFFFFFFFFull)
+        return -2;
+    DColBoost cb{};
+    try {
+        vqreq::RequestBoostPart b;
+        if (fun != BF_NONE) b.boost_fun = vqreq::BoostFunction(fun);  // enum order matches BoostFun
+        b.param = param;
+        if (n_skip) b.skip_when_score = std::vector<float>(skip, skip + n_skip);
+        if (expression) b.expression = std::string(expression);
+        fill_boost_params(cb, b);
+    } catch (const std::exception& e) {
+        g_err = e.what();  // (a bad expression, more than 4 skip values)
+        return -2;
+    }
+    return vq::debug_col_boost(cb, values, num_keys, present_words, key_base, docs, scores, n, out_scores, out_log10_factor);
 }
 /* self-check (tests): the facet top-`top` kernels on a caller's histogram */
 int vq_debug_facet_select(const uint32_t* hist, uint32_t num_values, uint32_t top, uint32_t misalign, uint32_t* out_values, uint32_t* out_counts) {

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <thread>
 
 #include "engine.hpp"
@@ -1840,9 +1841,13 @@ void finish_batch(const Index& idx, PartialBatch& pb, const void* gathered_devic
         const uint32_t have = reinterpret_cast<const uint32_t*>(hd + o_n)[q];
         const uint32_t* ids = reinterpret_cast<const uint32_t*>(hd + o_ids) + key_off;
         const float* scores = reinterpret_cast<const float*>(hd + o_scores) + key_off;
+        // top_n_sort (sort.rs:5-22) starts from worst_score = f32::MIN and passes over every hit below it: a hit whose score is -inf (a Log boost
+        // of a column value 0) counts in num_hits and is never returned.  Such hits rank last: they are the tail of the ranked window
+        uint32_t returnable = have;
+        while (returnable && scores[returnable - 1] < -std::numeric_limits<float>::max()) --returnable;
         // apply_top_skip (search.rs:230-239) on the top+skip window
         const uint32_t want = cq.top + cq.skip;
-        const uint32_t avail = std::min(have, want);
+        const uint32_t avail = std::min(returnable, want);
         const uint32_t from = std::min(cq.skip, avail);
         const uint32_t to = std::min(avail, from + cq.top);
         r->ids.assign(ids + from, ids + to);

@@ -122,6 +122,58 @@ __device__ float apply_col_boost(float score, const DColBoost& cb, uint32_t doc)
     return apply_boost_value(score, cb, as_global(cb.values)[row]);
 }
 
+// self-check (tests): the boost arithmetic of the scans alone — element i takes apply_col_boost(scores[i], cb, docs[i]) and, for a doc with a
+// present row, the factor k_explain records for a Log10 boost (0.0f for a doc without one).  One lane per element.
+__global__ void k_col_boost_check(const DColBoost* __restrict__ cbp, const uint32_t* __restrict__ docs, const float* __restrict__ scores, uint32_t n,
+                                  float* __restrict__ out_scores, float* __restrict__ out_log10_factor) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DColBoost& cb = *cbp;
+    const uint32_t doc = docs[i];
+    out_scores[i] = apply_col_boost(scores[i], cb, doc);
+    float factor = 0.0f;
+    if (doc >= cb.key_base && doc - cb.key_base < cb.num_keys) {
+        const uint32_t row = doc - cb.key_base;
+        if (!cb.present || ((cb.present[row >> 5] >> (row & 31u)) & 1u)) factor = log10_f32(cb.values[row] + cb.param);
+    }
+    out_log10_factor[i] = factor;
+}
+// `cb` carries the request's parameters (fill_boost_params); the column is staged here: `values` (num_keys f32) and `present_words`
+// ((num_keys + 31) / 32 words, or null) on the host.  0; -1 on a device error
+int debug_col_boost(DColBoost cb, const float* values, uint32_t num_keys, const uint32_t* present_words, uint32_t key_base, const uint32_t* docs, const float* scores,
+                    uint32_t n, float* out_scores, float* out_log10_factor) {
+    float *d_values = nullptr, *d_scores = nullptr, *d_out = nullptr, *d_factor = nullptr;
+    uint32_t *d_present = nullptr, *d_docs = nullptr;
+    DColBoost* d_cb = nullptr;
+    const size_t pw = (size_t(num_keys) + 31) / 32;
+    bool ok = hipMalloc(&d_values, size_t(num_keys) * 4 + 4) == hipSuccess && hipMalloc(&d_scores, size_t(n) * 4) == hipSuccess && hipMalloc(&d_out, size_t(n) * 4) == hipSuccess &&
+              hipMalloc(&d_factor, size_t(n) * 4) == hipSuccess && hipMalloc(&d_docs, size_t(n) * 4) == hipSuccess && hipMalloc(&d_cb, sizeof cb) == hipSuccess &&
+              (!present_words || hipMalloc(&d_present, pw * 4 + 4) == hipSuccess);
+    ok = ok && (!num_keys || hipMemcpy(d_values, values, size_t(num_keys) * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         (!present_words || !pw || hipMemcpy(d_present, present_words, pw * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         hipMemcpy(d_docs, docs, size_t(n) * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_scores, scores, size_t(n) * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        cb.values = d_values;
+        cb.present = d_present;
+        cb.key_base = key_base;
+        cb.num_keys = num_keys;
+        ok = hipMemcpy(d_cb, &cb, sizeof cb, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (ok) {
+        hipLaunchKernelGGL(k_col_boost_check, dim3((n + 255u) / 256u), dim3(256), 0, 0, d_cb, d_docs, d_scores, n, d_out, d_factor);
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_scores, d_out, size_t(n) * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_log10_factor, d_factor, size_t(n) * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(d_values);
+    (void)hipFree(d_scores);
+    (void)hipFree(d_out);
+    (void)hipFree(d_factor);
+    (void)hipFree(d_docs);
+    (void)hipFree(d_present);
+    (void)hipFree(d_cb);
+    return ok ? 0 : -1;
+}
+
 constexpr uint32_t kFacetCache = 1024;  // slots of the per-workgroup facet counter cache (keys + counts: 8 KB)
 // Facet counting (persistence.rs:164-175): a hit adds one to the histogram entry of each of its values.  Hot values (a Zipf-skewed category
 // field) would serialise on single HBM words; the workgroup keeps a direct-mapped counter cache in LDS — a value takes the slot its index

@@ -319,6 +319,48 @@ void vq_docset_aggs_free(vq_docset_aggs*);
 /* measurement: with VQ_DOCSET_TIMING=1 in the environment, the HIP event time (ms) of the kernels of this thread's last vq_docset_aggregate;
  * negative when none was launched or timed */
 float vq_debug_docset_aggregate_ms(void);
+/* A staged set ordered by a numeric column: rows [skip, skip + top) of the set's docs, selected on the device without a search and without a host
+ * copy of the column.  spec_json: {"field": "price", "top": 10, "skip": 0, "descending": false, "with_missing": true} (all but `field` optional,
+ * with these defaults).  `field` names the column "<field>.boost_valid_to_value", resolved exactly as vq_docset_from_ranges and
+ * vq_docset_aggregate resolve it, with their errors.  Every doc of the set gets one 32-bit sort key: a doc with a number the order-preserving key
+ * of its f32 (ascending) or that key's complement (descending) — -0 and +0 share a key, the infinities are numbers; a doc whose value is NaN
+ * 0xFFFFFFFE in both directions; a doc without a value (below key_base, behind the last key, presence bit clear) 0xFFFFFFFF.  The order is sort key
+ * ascending, then doc id ascending: in both directions numbers, then NaN docs, then missing docs, ties always by ascending doc id.  A field with
+ * "[]" (keyed by value id, joined through "<field>.value_id_to_anchor", first entry of the row, as the aggregations read it): a doc's key is the
+ * smallest sort key among its present values — its minimum when ascending, its maximum when descending —, the NaN key when all its present values
+ * are NaN, the missing key when it has none.  with_missing false lists only docs with a number; a page past them is short or empty.  The rows:
+ * vq_docset_top_len of them, vq_docset_top_docs / _values / _kinds in row order (owned by the handle): kind 0 a number, 1 NaN, 2 missing; value
+ * the f32 recovered from the key (a zero is +0.0), NaN for kind 1, 0.0 for kind 2.  vq_docset_top_counters writes docs, count, nan, missing (in
+ * docs of the set, docs = count + nan + missing; for a column keyed by doc the numbers of vq_docset_aggregate).  The result is a pure function of
+ * the inputs: two calls give identical rows, nothing depends on the order of atomics.  top + skip <= 65536 (the search's bound on ranked hits):
+ * above it VQ_ERR_UNSUPPORTED; top = 0 returns counters and no rows.  VQ_ERR_JSON for text that does not parse or a value of the wrong type;
+ * VQ_ERR_INVALID_ARGUMENT for a null argument, a spec without `field`, an unknown key, a negative or fractional top / skip, a ".token_values"
+ * column, a set of another index; the search's VQ_ERR_INDEX_NOT_FOUND for an unknown column or a 1:n field without its value_id_to_anchor store.
+ * Synchronous; any number of threads may call concurrently, also on one set, which is only read; a call owns its scratch: 4 bytes per local id,
+ * and for a field with "[]" 4 bytes per doc of the index's doc range.  VQ_TOP_MAX_GRID=<n> (read at every call; tests) caps the workgroups of every
+ * kernel, VQ_TOP_FORCE_SELECT=1 (read at every call; tests) runs the select even when the set holds no more than top + skip docs.
+ * Shards: a top-k is no sum, so no hook is called.  On a sharded index the call returns the shard's part: its own first top + skip rows with skip
+ * not applied, its local counters (docs = the set's docs inside the shard), vq_docset_top_is_partial 1.  vq_docset_top_merge (host only) merges
+ * the parts of all shards by (sort key, doc), applies skip and top and sums the counters; VQ_ERR_INVALID_ARGUMENT for no part, a null part, or
+ * parts whose top, skip, direction, with_missing or field differ.  vq_docset_top_pack writes a part's flat byte image (a fixed 64-byte header,
+ * the field, the rows as (sort key, doc) pairs) to out when cap suffices and returns the bytes needed (0: an error), so that ranks in different
+ * processes can all-gather it; vq_docset_top_unpack validates every length, the counters and the order of the rows and answers
+ * VQ_ERR_INVALID_ARGUMENT for a malformed image. */
+typedef struct vq_docset_top vq_docset_top;
+int vq_docset_top_by(const vq_index*, const vq_docset*, const char* spec_json, size_t len, vq_docset_top** out);
+size_t vq_docset_top_len(const vq_docset_top*);
+const uint32_t* vq_docset_top_docs(const vq_docset_top*);
+const float* vq_docset_top_values(const vq_docset_top*);
+const uint8_t* vq_docset_top_kinds(const vq_docset_top*);
+void vq_docset_top_counters(const vq_docset_top*, uint64_t* out4); /* docs, count, nan, missing */
+int vq_docset_top_is_partial(const vq_docset_top*);
+int vq_docset_top_merge(const vq_docset_top* const* parts, size_t n, vq_docset_top** out);
+size_t vq_docset_top_pack(const vq_docset_top*, uint8_t* out, size_t cap);
+int vq_docset_top_unpack(const uint8_t* bytes, size_t len, vq_docset_top** out);
+void vq_docset_top_free(vq_docset_top*);
+/* measurement: with VQ_DOCSET_TIMING=1 in the environment, the HIP event time (ms) of the kernels of this thread's last vq_docset_top_by;
+ * negative when none was launched or timed */
+float vq_debug_docset_top_ms(void);
 /* `SearchResult.why_found_terms` (src/search/result/search_result.rs:21-25, filled at src/search.rs:186 when the request says
  * `why_found: true`): per text index path the matched dictionary terms, as JSON {"<path>": ["term", ...]} (thread-local string;
  * the reference's map and list orders are unspecified). */

@@ -27,6 +27,8 @@ SYMBOLS = [
     "vq_docset_create", "vq_docset_from_filter", "vq_docset_len", "vq_docset_local_len", "vq_docset_device_bytes", "vq_debug_docset_part", "vq_debug_docset_timings", "vq_docset_free",
     "vq_request_set_docset", "vq_docset_combine", "vq_docset_ids", "vq_debug_docset_route", "vq_docset_facets", "vq_debug_docset_facets_count_ms", "vq_docset_from_ranges", "vq_debug_docset_range_route",
     "vq_docset_aggregate", "vq_docset_aggs_len", "vq_docset_aggs_get", "vq_docset_aggs_free", "vq_debug_docset_aggregate_ms",
+    "vq_docset_top_by", "vq_docset_top_len", "vq_docset_top_docs", "vq_docset_top_values", "vq_docset_top_kinds", "vq_docset_top_counters", "vq_docset_top_is_partial",
+    "vq_docset_top_merge", "vq_docset_top_pack", "vq_docset_top_unpack", "vq_docset_top_free", "vq_debug_docset_top_ms",
 ]
 COMM_ID_BYTES = 128
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -186,6 +188,18 @@ def lib():
         "vq_docset_aggs_get": (C.POINTER(DocsetAgg), [vp, sz]),
         "vq_docset_aggs_free": (None, [vp]),
         "vq_debug_docset_aggregate_ms": (C.c_float, []),
+        "vq_docset_top_by": (i, [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(vp)]),
+        "vq_docset_top_len": (sz, [vp]),
+        "vq_docset_top_docs": (vp, [vp]),
+        "vq_docset_top_values": (vp, [vp]),
+        "vq_docset_top_kinds": (vp, [vp]),
+        "vq_docset_top_counters": (None, [vp, C.POINTER(u64)]),
+        "vq_docset_top_is_partial": (i, [vp]),
+        "vq_docset_top_merge": (i, [C.POINTER(vp), sz, C.POINTER(vp)]),
+        "vq_docset_top_pack": (sz, [vp, vp, sz]),
+        "vq_docset_top_unpack": (i, [vp, sz, C.POINTER(vp)]),
+        "vq_docset_top_free": (None, [vp]),
+        "vq_debug_docset_top_ms": (C.c_float, []),
     }
     for name, (rt, at) in sig.items():
         f = getattr(L, name)

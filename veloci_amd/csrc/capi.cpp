@@ -641,6 +641,67 @@ size_t vq_docset_aggs_len(const vq_docset_aggs* a) { return a ? a->c.size() : 0;
 const vq_docset_agg* vq_docset_aggs_get(const vq_docset_aggs* a, size_t i) { return a && i < a->c.size() ? &a->c[i] : nullptr; }
 void vq_docset_aggs_free(vq_docset_aggs* a) { delete a; }
 float vq_debug_docset_aggregate_ms(void) { return vq::docset_aggregate_last_ms(); }
+int vq_docset_top_by(const vq_index* index, const vq_docset* d, const char* spec_json, size_t len, vq_docset_top** out) {
+    return guard([&] {
+        if (!index || !d || !spec_json || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_top_by: null argument");
+        *out = nullptr;
+        vq::TopSpec spec;
+        try {
+            spec = vq::top_spec_from_json(vqjson::parse(spec_json, len));
+        } catch (const vqjson::ParseError& e) {
+            throw VelociError(VQ_ERR_JSON, std::string("JsonError: ") + e.what());
+        }
+        const std::shared_ptr<const DocSet> set = d->set;  // held for the length of the call
+        auto h = std::make_unique<vq_docset_top>();
+        h->r = vq::docset_top(*index->idx, *set, spec);
+        *out = h.release();
+    });
+}
+size_t vq_docset_top_len(const vq_docset_top* t) { return t ? t->r.docs.size() : 0; }
+const uint32_t* vq_docset_top_docs(const vq_docset_top* t) { return t ? t->r.docs.data() : nullptr; }
+const float* vq_docset_top_values(const vq_docset_top* t) { return t ? t->r.values.data() : nullptr; }
+const uint8_t* vq_docset_top_kinds(const vq_docset_top* t) { return t ? t->r.kinds.data() : nullptr; }
+void vq_docset_top_counters(const vq_docset_top* t, uint64_t* out4) {
+    if (!out4) return;
+    out4[0] = t ? t->r.n_docs : 0;
+    out4[1] = t ? t->r.count : 0;
+    out4[2] = t ? t->r.nan : 0;
+    out4[3] = t ? t->r.missing : 0;
+}
+int vq_docset_top_is_partial(const vq_docset_top* t) { return t && t->r.partial ? 1 : 0; }
+int vq_docset_top_merge(const vq_docset_top* const* parts, size_t n, vq_docset_top** out) {
+    return guard([&] {
+        if (!out || (n && !parts)) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_top_merge: null argument");
+        *out = nullptr;
+        std::vector<const vq::TopResult*> p(n);
+        for (size_t i = 0; i < n; ++i) p[i] = parts[i] ? &parts[i]->r : nullptr;
+        auto h = std::make_unique<vq_docset_top>();
+        h->r = vq::docset_top_merge(p);
+        *out = h.release();
+    });
+}
+size_t vq_docset_top_pack(const vq_docset_top* t, uint8_t* out, size_t cap) {
+    if (!t) return 0;
+    size_t need = 0;
+    if (guard([&] {
+            const std::vector<uint8_t> image = vq::docset_top_pack(t->r);
+            need = image.size();
+            if (out && cap >= need) std::memcpy(out, image.data(), need);
+        }) != VQ_OK)
+        return 0;  // (the reason is in vq_last_error)
+    return need;
+}
+int vq_docset_top_unpack(const uint8_t* bytes, size_t len, vq_docset_top** out) {
+    return guard([&] {
+        if (!bytes || !out) throw VelociError(VQ_ERR_INVALID_ARGUMENT, "vq_docset_top_unpack: null argument");
+        *out = nullptr;
+        auto h = std::make_unique<vq_docset_top>();
+        h->r = vq::docset_top_unpack(bytes, len);
+        *out = h.release();
+    });
+}
+void vq_docset_top_free(vq_docset_top* t) { delete t; }
+float vq_debug_docset_top_ms(void) { return vq::docset_top_last_ms(); }
 int vq_debug_docset_route(const vq_docset* d) { return d ? d->set->route : -1; }
 uint64_t vq_docset_len(const vq_docset* d) { return d ? d->set->len : 0; }
 uint64_t vq_docset_local_len(const vq_docset* d) { return d ? d->set->local_len : 0; }

@@ -29,6 +29,9 @@ struct vq_docset_aggs {
     std::vector<vq::AggResult> r;  // the buckets the C structs point into
     std::vector<vq_docset_agg> c;
 };
+struct vq_docset_top {
+    vq::TopResult r;
+};
 struct vq_partial_batch {
     std::unique_ptr<vq::PartialBatch> pb;
 };

@@ -726,6 +726,39 @@ std::vector<AggResult> docset_aggregate(const Index& idx, const DocSet& ds, cons
 double agg_limbs_to_double(const uint64_t* pos, const uint64_t* neg);
 // VQ_DOCSET_TIMING=1: the HIP event time (ms) of the kernels of this thread's last docset_aggregate; negative: none was launched or timed
 float docset_aggregate_last_ms();
+// A staged set ordered by a column (docset_top.cpp, docset_top.hip): rows [skip, skip + top) of the set's docs in the order (sort key ascending,
+// doc ascending).  The sort key (kernels.hpp): range_key of the value (descending: its complement), kTopNanKey for a NaN, kTopMissingKey for a doc
+// without a value; a 1:n doc gets the smallest sort key of its present values — so both directions list numbers, then NaN docs, then missing
+// docs, ties by ascending doc id.  with_missing false: only docs with a number.  top + skip <= kTopMaxRows, else ERR_UNSUPPORTED.  Synchronous, on
+// pre_stream (else stream); each call owns its scratch (4 B per local id, and for a 1:n field 4 B per doc of the index's doc range).  On a
+// sharded index the result is the shard's part: its own first top + skip rows with skip not applied, its local counters, partial = true; no hook
+// is called.  docset_top_merge puts parts together on the host
+struct TopSpec {
+    std::string field;
+    uint32_t top = 10, skip = 0;
+    bool descending = false, with_missing = true;
+};
+struct TopResult {
+    TopSpec spec;
+    bool partial = false;
+    std::vector<uint32_t> docs, keys;  // the rows: doc and sort key
+    std::vector<float> values;         // value_of_key for a number (a zero is +0.0), NaN for a NaN doc, 0.0 for a missing one
+    std::vector<uint8_t> kinds;        // 0 number, 1 NaN, 2 missing
+    uint64_t n_docs = 0, count = 0, nan = 0, missing = 0;  // in docs of the local set (a merge: of all parts); n_docs = count + nan + missing
+};
+// the spec of vq_docset_top_by: throws vqjson::ParseError for a value of the wrong type, ERR_INVALID_ARGUMENT for a spec without `field`, an
+// unknown key or a top / skip that is no unsigned 32-bit integer
+TopSpec top_spec_from_json(const vqjson::Value& v);
+TopResult docset_top(const Index& idx, const DocSet& ds, const TopSpec& spec);
+// host only: the parts of one call on every shard -> the whole index's page.  ERR_INVALID_ARGUMENT for no part, a null part, a part that is not
+// partial beside others, parts whose top, skip, direction, with_missing or field differ
+TopResult docset_top_merge(const std::vector<const TopResult*>& parts);
+// a result as a flat byte image (a fixed header, the field, the rows as (sort key, doc) pairs) and back; unpack validates every length and the
+// order of the rows and throws ERR_INVALID_ARGUMENT for a malformed image
+std::vector<uint8_t> docset_top_pack(const TopResult& r);
+TopResult docset_top_unpack(const uint8_t* bytes, size_t len);
+// VQ_DOCSET_TIMING=1: the HIP event time (ms) of the kernels of this thread's last docset_top; negative: none was launched or timed
+float docset_top_last_ms();
 // The set's local ids (sorted, unique, unpadded): min(local_len, cap) of them to `out`, host memory or (on_device) memory of the set's GPU — then
 // device to device on the set's stream, finished on return.  Returns local_len
 uint64_t copy_docset_ids(const DocSet& ds, uint32_t* out, uint64_t cap, bool on_device);

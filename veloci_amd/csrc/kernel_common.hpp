@@ -148,6 +148,16 @@ __device__ __forceinline__ uint32_t wave_excl_scan_u32(uint32_t x, uint32_t* tot
     return incl - x;
 }
 
+// hist[bin] += 1 for every lane with `live`; lanes of one wave that share the first live lane's bin add their count once
+__device__ __forceinline__ void hist_add(uint32_t* hist, bool live, uint32_t bin) {
+    const unsigned long long all = __ballot(live);
+    if (!all) return;
+    const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)__builtin_ctzll(all));
+    const unsigned long long same = __ballot(live && bin == lead);
+    if (lane_id() == (uint32_t)__builtin_ctzll(all)) atomicAdd(hist + lead, (uint32_t)__popcll(same));
+    if (live && bin != lead) atomicAdd(hist + bin, 1u);
+}
+
 // A DOp fetched as ten dwords through the constant address space (scalar loads), fields decoded with scalar shifts.
 struct KOp {
     uint32_t r0, r1;

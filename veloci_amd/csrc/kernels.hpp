@@ -301,6 +301,53 @@ void launch_docset_agg_ids(hipStream_t st, const uint32_t* docs, uint32_t local_
 // the doc in kAggHas.  max_keys: the largest num_keys of the m columns
 void launch_docset_agg_values(hipStream_t st, const DocsetAggD* aggs, uint32_t m, uint32_t max_keys, const uint32_t* member, uint32_t member_word0, uint32_t doc_lo,
                               uint32_t doc_hi, unsigned long long* state, uint32_t* mm, bool prereduce, uint32_t max_grid = 0);
+// ---- doc sets ordered by a column (docset_top.hip): the first K rows of a staged set's docs in the order (sort key ascending, doc ascending).
+// The sort key of a doc: range_key(bits) of its value (descending: ~range_key(bits); both in [kRangeKeyMin, kRangeKeyMax]), kTopNanKey for a NaN,
+// kTopMissingKey for a doc without a value; a 1:n doc gets the smallest sort key of its present values.  A call owns its scratch:
+//   keys    the sort key of every local id (u32, local_len rounded up to whole 16-byte vectors; the padding holds kTopMissingKey, never counted)
+//   hist    4 histograms of 256 bins, one per byte of the key from the top byte down (zeroed before the launch)
+//   chunks  per workgroup of the tie kernels the keys == T of its contiguous chunk
+//   state   kTopStateWords u32 (zeroed, or preset for a call without select): the three counters, the emit cursor, the agreed prefix, the rows
+//           still wanted, then the outcome of the select: the threshold key T, B = keys < T, E = keys == T, the ties to take (rows wanted - B),
+//           whether all ties are taken (E == take: they go through the cursor), done (nothing is wanted: nothing is emitted)
+constexpr uint32_t kTopNanKey = 0xFFFFFFFEu, kTopMissingKey = 0xFFFFFFFFu;
+constexpr uint32_t kTopMaxRows = 65536;  // top + skip of one call: the search's own bound on ranked hits
+constexpr uint32_t kTopMaxGrid = 2048;   // workgroups of one wave per kernel; the rest of the work is strided
+constexpr uint32_t kTopCount = 0, kTopNan = 1, kTopMissing = 2, kTopCursor = 3, kTopPrefix = 4, kTopWant = 5, kTopT = 6, kTopB = 7, kTopE = 8, kTopTake = 9, kTopAllTies = 10,
+                   kTopDone = 11, kTopStateWords = 16;
+struct DocsetTopD {
+    const uint32_t* values;   // the column's f32 bit patterns (1:n: 16-byte aligned, a vector of slack behind them)
+    const uint32_t* present;  // presence bitmap over the rows, or null: every row is present
+    const uint64_t* a_off;    // 1:n: the value_id_to_anchor table (row r = value id a_key_base + r), the first entry of a row is the value's anchor
+    const uint32_t* a_vals;
+    const uint32_t* best;     // 1:n, k_top_keys: the folded sort key of doc d at best[d - doc_lo], read in place of the column
+    uint32_t key_base, num_keys;
+    uint32_t a_key_base, a_num_keys;
+    uint32_t doc_lo, descending;
+};
+inline uint32_t top_grid(uint64_t vectors, uint32_t max_grid) {  // workgroups of 64 lanes, one 16-byte vector per lane and round
+    const uint64_t waves = (vectors + 63u) / 64u;
+    const uint32_t cap = max_grid ? (max_grid < kTopMaxGrid ? max_grid : kTopMaxGrid) : kTopMaxGrid;
+    return uint32_t(waves < cap ? (waves ? waves : 1u) : cap);
+}
+// 1:n: best[anchor - doc_lo] = min(best, sort key) for every present value whose anchor lies in [doc_lo, doc_hi) and in `member` (bit of doc d in
+// word (d >> 5) - member_word0); best: doc_hi - doc_lo words preset to kTopMissingKey
+void launch_top_fold(hipStream_t st, const DocsetTopD& a, const uint32_t* member, uint32_t member_word0, uint32_t doc_hi, uint32_t* best, uint32_t max_grid);
+// keys[i] = the sort key of docs[i] (docs: sorted, 16-byte aligned, padded to a multiple of 4 entries, all inside the index's doc range); hist[top
+// byte] and the three counters of `state` count the local_len real entries
+void launch_top_keys(hipStream_t st, const uint32_t* docs, uint32_t local_len, const DocsetTopD& a, uint32_t* keys, uint32_t* hist, uint32_t* state, uint32_t max_grid);
+// one wave: the digit at `shift` (24, 16, 8, 0) of the threshold from this pass's histogram.  shift 24 first sets the rows wanted to min(rows,
+// with_missing ? n : state[kTopCount]); shift 0 leaves T, B, E, take and all-ties
+void launch_top_pick(hipStream_t st, uint32_t* state, const uint32_t* hist, uint32_t shift, uint32_t rows, bool with_missing, uint32_t n);
+// hist[byte at shift] += 1 for every of the n keys whose higher bytes equal state[kTopPrefix] (shift 16, 8, 0)
+void launch_top_hist(hipStream_t st, const uint32_t* keys, uint32_t n, uint32_t shift, const uint32_t* state, uint32_t* hist, uint32_t max_grid);
+// the ties: workgroup c owns the vectors [c * vpc, (c + 1) * vpc) of keys / docs, vpc = ceil(vectors / grid), grid = top_grid(vectors, max_grid) in
+// both launches.  chunks[c] = its keys == T (left alone when all ties are taken or none is)
+void launch_top_tiecount(hipStream_t st, const uint32_t* keys, uint32_t n, const uint32_t* state, uint32_t* chunks, uint32_t max_grid);
+// out[..] = key << 32 | doc: every key < T through the cursor (no order), then the first `take` keys == T in doc order at out[B ..); when all ties
+// are taken they go through the cursor too.  Nothing is written at or behind out[cap]
+void launch_top_emit(hipStream_t st, const uint32_t* docs, const uint32_t* keys, uint32_t n, uint32_t* state, const uint32_t* chunks, unsigned long long* out, uint32_t cap,
+                     uint32_t max_grid);
 
 // ---- text locality pre-pass (K7)
 struct LocRow {  // copy table[src .. src + len) to the gather buffer at dst

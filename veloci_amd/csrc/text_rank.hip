@@ -36,16 +36,6 @@ __global__ __launch_bounds__(256) void k_text_best(const TextRowD* __restrict__ 
     }
 }
 
-// hist[bin] += 1 for every lane with `live`; lanes of one wave that share the first live lane's bin add their count once
-__device__ __forceinline__ void hist_add(uint32_t* hist, bool live, uint32_t bin) {
-    const unsigned long long all = __ballot(live);
-    if (!all) return;
-    const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)__builtin_ctzll(all));
-    const unsigned long long same = __ballot(live && bin == lead);
-    if (lane_id() == (uint32_t)__builtin_ctzll(all)) atomicAdd(hist + lead, (uint32_t)__popcll(same));
-    if (live && bin != lead) atomicAdd(hist + bin, 1u);
-}
-
 __global__ __launch_bounds__(kSelectThreads) void k_text_select(const uint32_t* __restrict__ best, uint32_t num_texts, const uint32_t* __restrict__ top_ns, uint32_t out_stride,
                                                                 uint32_t* __restrict__ out_counts, uint32_t* __restrict__ out_pairs) {
     __shared__ uint32_t hist[256];

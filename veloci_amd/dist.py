@@ -466,3 +466,13 @@ def search_shards_local(shards, requests, docsets=None):
             if isinstance(r, Exception):
                 raise r
     return results
+
+
+def top_by_shards_local(shards, sets, field, **kw):
+    """`DocSet.top_by` over every doc-range shard in THIS process (tests, single-GPU rehearsals): sets[s] is the DocSet made on shards[s]; every
+    shard answers its part, the parts travel as packed bytes (what ranks in different processes would all-gather) and `merge_top_by` merges
+    them.  No hook is needed: a top-k is no sum.  kw: top, skip, descending, with_missing."""
+    from .search import merge_top_by
+    if len(sets) != len(shards):
+        raise ValueError("sets: one DocSet per shard")
+    return merge_top_by([ds.top_by(field, **kw).pack() for ds in sets])

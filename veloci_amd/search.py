@@ -278,6 +278,17 @@ class DocSet:
         """-> len(edges) + 1 ints: the set's values of `field` below edges[0], in [edges[i-1], edges[i]), at or above edges[-1]"""
         return self.aggregate([{"field": field, "edges": [float(e) for e in edges]}])[0]["buckets"]
 
+    def top_by(self, field, top=10, skip=0, descending=False, with_missing=True):
+        """Rows [skip, skip + top) of the set's docs ordered by the column `<field>.boost_valid_to_value` (`vq_docset_top_by`), selected on the
+        index's GPU -> TopByResult.  The order: docs with a number by value (ascending, or descending), then docs whose value is NaN, then docs
+        without a value, ties (-0 equals +0) always by ascending doc id.  A field with "[]" orders a doc by its smallest value when ascending and
+        by its largest when descending.  `with_missing=False` lists only docs with a number.  top + skip <= 65536.  On a sharded index the result
+        is the shard's part (`partial`): its own first top + skip rows; `merge_top_by` puts the parts of all shards together, no hook is needed."""
+        spec = json.dumps({"field": field, "top": top, "skip": skip, "descending": descending, "with_missing": with_missing}).encode()
+        h = C.c_void_p()
+        _lib.check(self.L.vq_docset_top_by(self.index.h, self._handle(), spec, len(spec), C.byref(h)))
+        return TopByResult(self.L, h)
+
     def timings(self):
         """(mark, count + scan, expand) in ms, recorded when the set was made with VQ_DOCSET_TIMING=1 in the environment; else None"""
         a, b, c = C.c_float(), C.c_float(), C.c_float()
@@ -295,6 +306,75 @@ class DocSet:
             self.close()
         except Exception:
             pass
+
+
+class TopByResult:
+    """The page of `DocSet.top_by` / `merge_top_by` (`vq_docset_top`): numpy arrays `docs` (uint32), `values` (float32: NaN for a NaN doc, 0.0 for a
+    missing one), `kinds` (uint8: 0 number, 1 NaN, 2 missing) in row order; `counters`: dict(docs, count, nan, missing) in docs of the set (a
+    shard's part: of the set's docs inside the shard); `partial`: a shard's part, to be merged; `pack()`: the flat byte image of the result."""
+
+    def __init__(self, L, h):
+        self.L, self.h, self._image = L, h, None
+        n = int(L.vq_docset_top_len(h))
+
+        def arr(ptr, dtype):
+            return np.frombuffer(C.string_at(ptr, n * np.dtype(dtype).itemsize), dtype=dtype) if n else np.zeros(0, dtype)
+
+        self.docs = arr(L.vq_docset_top_docs(h), np.uint32)
+        self.values = arr(L.vq_docset_top_values(h), np.float32)
+        self.kinds = arr(L.vq_docset_top_kinds(h), np.uint8)
+        c = (C.c_uint64 * 4)()
+        L.vq_docset_top_counters(h, c)
+        self.counters = {"docs": int(c[0]), "count": int(c[1]), "nan": int(c[2]), "missing": int(c[3])}
+        self.partial = bool(L.vq_docset_top_is_partial(h))
+
+    def __len__(self):
+        return int(self.docs.size)
+
+    def pack(self):
+        """the flat byte image (`vq_docset_top_pack`): what ranks in different processes all-gather; `merge_top_by` takes it as it takes the object"""
+        if self._image is None:
+            need = int(self.L.vq_docset_top_pack(self.h, None, 0))
+            image = C.create_string_buffer(max(need, 1))
+            if not need or int(self.L.vq_docset_top_pack(self.h, image, need)) != need:
+                raise VelociError(6, self.L.vq_last_error().decode() or "vq_docset_top_pack failed")
+            self._image = image.raw[:need]
+        return self._image
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.vq_docset_top_free(self.h)
+            self.h = None
+
+    def rows(self):
+        """[(doc, value, kind)]"""
+        return list(zip(self.docs.tolist(), self.values.tolist(), self.kinds.tolist()))
+
+
+def merge_top_by(parts):
+    """The parts of one `DocSet.top_by` call on every shard (TopByResult objects or their packed bytes) -> the whole index's page
+    (`vq_docset_top_merge`, host only): merged by (sort key, doc), skip and top applied, the counters summed.  Parts whose top, skip, direction,
+    with_missing or field differ are refused (VelociError, InvalidArgument), as is a malformed image."""
+    L = _lib.lib()
+    parts = list(parts)
+    own = []  # the handles unpacked here; a result object lends its own
+    try:
+        handles = []
+        for p in parts:
+            if isinstance(p, TopByResult):
+                handles.append(p.h)
+                continue
+            image = bytes(p)
+            h = C.c_void_p()
+            _lib.check(L.vq_docset_top_unpack(image, len(image), C.byref(h)))
+            own.append(h)
+            handles.append(h)
+        out = C.c_void_p()
+        _lib.check(L.vq_docset_top_merge((C.c_void_p * max(len(handles), 1))(*handles), len(handles), C.byref(out)))
+        return TopByResult(L, out)
+    finally:
+        for h in own:
+            L.vq_docset_top_free(h)
 
 
 class Request:
